@@ -21,7 +21,13 @@ the library's RCCL loop (ddrl_ppo_update_ddp) by default, DDRL_DDP_LOOP=python f
 loop, --ddp-mode split | local (ddrl_amd/ddp.py).  DDRL_FORCE_DDP=1 runs that learner at one rank
 (under torchrun) and DDRL_DIST_BACKEND=gloo rehearses N ranks on one GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--env NAME] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--env NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what
+takes runs of its own after the timed region: as many iterations again with the envs stepped on
+the host (pcie_inclusive; --no-pcie leaves it out) and the numpy oracle's CPU baselines
+(cpu_baseline, cpu_baseline_all_cores; --no-cpu-baseline leaves them out).  --dump-outputs DIR
+writes the state the last timed step left (dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -328,6 +334,44 @@ def cpu_baseline_parallel(env, n_envs=512, T=200, workers=16, seed=0):
     return T * n_envs / dt, dt, len(chunks)
 
 
+DUMP_ROWS = 4096   # record rows per policy that --dump-outputs keeps
+
+
+def dump_outputs(out_dir, lctx, rctx, kl, stats_steps, suffix=""):
+    """What the last timed iteration left with its caller, as <out_dir>/<name><suffix>.npy (fp32
+    as the library holds it, the KL coefficients fp64), per policy p of the learner context:
+      params_p       the updated flat parameter vector,
+      adam_m_p, adam_v_p  the optimizer's moments after the update,
+      stats_p        the learner statistics of every minibatch step of the update [steps][8]
+                     (stats_steps = None, the data-parallel learner: not kept),
+      records_p      DUMP_ROWS rows of the train batch the update ran over (rollout + GAE: obs,
+                     action, logits, logp, value, advantage, value target, reward), a fixed seeded
+                     sample of the T * C rows in ascending order,
+      last_values_p  the bootstrap values V(s_T) of the rollout context rctx (this rank's envs),
+      adv_norm_p     the advantage standardization constants (mean, denominator),
+    and kl_coeff, every policy's KL coefficient after update_kl.  A few MB in all."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+    for p in range(lctx.cfg.n_policies):
+        save(f"params_{p}", lctx.params_get(p))
+        m, v, _, _ = lctx.adam_get(p)
+        save(f"adam_m_{p}", m)
+        save(f"adam_v_{p}", v)
+        if stats_steps is not None:
+            save(f"stats_{p}", lctx.ppo_stats(p, stats_steps))
+        rec = lctx.records_tensor(p)
+        rows = np.sort(np.random.default_rng(4242 + p).choice(rec.shape[0], min(DUMP_ROWS, rec.shape[0]),
+                                                              replace=False))
+        save(f"records_{p}", rec[torch.from_numpy(rows).to(rec.device)].cpu().numpy())
+        save(f"last_values_{p}", rctx.last_values_get(p))
+        save(f"adv_norm_{p}", lctx.adv_norm_get(p))
+    save("kl_coeff", np.asarray(kl, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -336,8 +380,15 @@ def main():
     ap.add_argument("--envs", type=int, default=4096, help="total envs over all ranks")
     ap.add_argument("--env", default="QuantrupedMultiEnv_Local")
     ap.add_argument("--frag", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-buffer (PCIe-inclusive) iteration")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the host-env (PCIe-inclusive) iterations and the CPU "
+                         "baselines and add them to the result line (default: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (parameters, Adam moments, learner statistics, a "
+                         "seeded sample of the train batch; see dump_outputs) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-pcie", action="store_true",
+                    help="with --full: skip the host-buffer (PCIe-inclusive) iteration")
     ap.add_argument("--cpu-envs", type=int, default=512)
     ap.add_argument("--sgd-iter", type=int, default=None,
                     help="profiling aid: num_sgd_iter of the run (default: the config's 10 epochs)")
@@ -351,6 +402,8 @@ def main():
                          "step) or 'auto' (default): gather for shared-policy envs -- the fastest exact mode "
                          "(DESIGN.md section 5) -- and replicas for independent-policy envs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -545,8 +598,12 @@ def main():
         dist.all_reduce(es)
         env_steps = int(es.item())
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, uctx or ctx, ctx, kl, None if ddp else steps_done[-1],
+                     f"_rank{rank}" if world > 1 else "")
+
     pcie = None
-    if world == 1 and not args.no_pcie and not ddp:
+    if args.full and world == 1 and not args.no_pcie and not ddp:
         # as many iterations again with the envs on the host (not part of value): pipelined host env
         # plane rollout + GAE + the same update
         torch.cuda.synchronize()
@@ -693,7 +750,7 @@ def main():
     }
     if pcie is not None:
         result["pcie_inclusive"] = pcie
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_envs = cpu_sample_envs(args.env, args.cpu_envs)
         v, dt, sample = cpu_baseline(args.env, cpu_envs, T)
         result["cpu_baseline"] = {"value": v, "unit": "env-steps/s", "cores": 1, "kind": "port",

@@ -19,9 +19,9 @@ trace trace --steps 2 --warmup 1 --no-cpu-baseline --no-pcie
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o run -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-pcie > $OUT/pmc_fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o run -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-pcie > $OUT/pmc_write.log 2>&1
 trace c4 --env QuantrupedMultiEnv_SharedDecentral --steps 1 --warmup 1 --no-cpu-baseline --no-pcie
-trace c5 --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 1 --warmup 1 --no-pcie
+trace c5 --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 1 --warmup 1 --no-pcie --full
 cd $R
 # the bench reports traffic from profiles/r01/pmc_update.json: refresh it from these passes
 python3 tools/pmc_summary.py $OUT > $OUT/pmc_update.json
 cp $OUT/pmc_update.json $R/profiles/r01/pmc_update.json
-timeout -k 10 400 python3 bench.py > $OUT/bench_default.log 2>&1
+timeout -k 10 400 python3 bench.py --full > $OUT/bench_default.log 2>&1

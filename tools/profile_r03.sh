@@ -20,11 +20,11 @@ pmc() {     # name, counter, bench args...
 }
 trace local --steps 2 --warmup 1 --no-cpu-baseline --no-pcie
 trace c4 --env QuantrupedMultiEnv_SharedDecentral --steps 1 --warmup 1 --no-cpu-baseline --no-pcie
-trace c5 --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 1 --warmup 1 --no-pcie
+trace c5 --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 1 --warmup 1 --no-pcie --full
 for c in FETCH_SIZE WRITE_SIZE; do
   pmc local $c --steps 1 --warmup 0 --no-cpu-baseline --no-pcie
   pmc c4 $c --env QuantrupedMultiEnv_SharedDecentral --steps 1 --warmup 0 --no-cpu-baseline --no-pcie
-  pmc c5 $c --env QuantrupedMultiEnv_DecentralShared_Graph --envs 128 --steps 1 --warmup 0 --no-pcie
+  pmc c5 $c --env QuantrupedMultiEnv_DecentralShared_Graph --envs 128 --steps 1 --warmup 0 --no-pcie --full
 done
 cd $R
 python3 tools/pmc_summary.py $OUT > $OUT/pmc_summary.json

@@ -13,7 +13,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 LOCAL="--steps 1 --warmup 0 --no-cpu-baseline --no-pcie"
 C4="--env QuantrupedMultiEnv_SharedDecentral --steps 1 --warmup 0 --no-cpu-baseline --no-pcie"
-C5="--env QuantrupedMultiEnv_DecentralShared_Graph --envs 128 --steps 1 --warmup 0 --no-pcie"
+C5="--env QuantrupedMultiEnv_DecentralShared_Graph --envs 128 --steps 1 --warmup 0 --no-pcie --full"
 trace() {   # name, bench args...
   local name=$1; shift
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -o run -- python3 $R/bench.py "$@" > $OUT/$name.log 2>&1 || return 1
@@ -34,6 +34,6 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 trace local --steps 2 --warmup 1 --no-cpu-baseline --no-pcie || exit 1
 trace c4 --env QuantrupedMultiEnv_SharedDecentral --steps 1 --warmup 1 --no-cpu-baseline --no-pcie || exit 1
-trace c5 --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 1 --warmup 1 --no-pcie || exit 1
+trace c5 --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 1 --warmup 1 --no-pcie --full || exit 1
 cd $R
 python3 tools/pmc_summary.py $OUT > $OUT/pmc_summary.json || exit 1

@@ -5,10 +5,10 @@ set -o pipefail
 O=gpurun_out/r05/bench
 mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.log 2>&1 || exit 1
+timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.log 2>&1 || exit 1
 tail -c 400 $O/bench_default.log; echo
-timeout -k 10 400 python3 bench.py --env QuantrupedMultiEnv_SharedDecentral --steps 2 --warmup 1 > $O/bench_c4.log 2>&1 || exit 1
-timeout -k 10 400 python3 bench.py --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 2 --warmup 1 > $O/bench_c5.log 2>&1 || exit 1
+timeout -k 10 400 python3 bench.py --env QuantrupedMultiEnv_SharedDecentral --steps 2 --warmup 1 --full > $O/bench_c4.log 2>&1 || exit 1
+timeout -k 10 400 python3 bench.py --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 2 --warmup 1 --full > $O/bench_c5.log 2>&1 || exit 1
 DDRL_GNN_TAIL=0 timeout -k 10 400 python3 bench.py --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 1 --warmup 1 --no-cpu-baseline --no-pcie > $O/bench_c5_3launch.log 2>&1 || exit 1
 for e in "QuantrupedMultiEnv_SharedDecentral 4096" "QuantrupedMultiEnv_DecentralShared_Graph 2048"; do
   set -- $e

@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest -v -s --timeout 580 --timeout-method threa
 rc=$?; echo "fullsize shared rc=$rc"; tail -5 $out/tests_fullsize_shared.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 300 python3 bench.py --env QuantrupedMultiEnv_DecentralShared_Graph --envs 2048 --steps 2 --warmup 1 \
-  --no-pcie > $out/bench_c5.log 2>&1 || exit $?
+  --no-pcie --full > $out/bench_c5.log 2>&1 || exit $?
 tail -c 1500 $out/bench_c5.log
 timeout -k 10 300 python3 bench.py --steps 2 --warmup 1 --no-pcie --no-cpu-baseline > $out/bench_default.log 2>&1 || exit $?
 tail -c 600 $out/bench_default.log

@@ -10,5 +10,5 @@ rc=$?; echo "gpu tests rc=$rc"; tail -3 $out/gpu_tests.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || exit $?
 tail -3 $out/smoke.log
-timeout -k 10 400 python3 bench.py > $out/bench_default.log 2>&1 || exit $?
+timeout -k 10 400 python3 bench.py --full > $out/bench_default.log 2>&1 || exit $?
 tail -c 1200 $out/bench_default.log
