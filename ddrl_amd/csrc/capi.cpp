@@ -116,6 +116,17 @@ struct ddrl_ctx {
   void* peer_ipc = nullptr;
   int32_t* peer_vsh = nullptr;
   size_t peer_vsh_n = 0;
+  // evaluation (ddrl_eval_*): per-env fp64 accumulators, episode counts, the result table
+  // [N][E][6], the two progress counters and the device copy of the env plane's kin buffer;
+  // ev_normc_ok: the filter constants are known current (no push since they were written)
+  int ev_on = 0;
+  ddrl_eval_cfg ev_cfg{};
+  double *ev_acc = nullptr, *ev_table = nullptr;
+  int32_t* ev_count = nullptr;
+  unsigned long long* ev_ctr = nullptr;
+  float* ev_kin = nullptr;
+  int ev_table_E = 0;
+  int ev_normc_ok = 0;
   std::vector<void*> allocs;
 };
 
@@ -546,6 +557,7 @@ int ddrl_filter_set(ddrl_ctx* c, double n, const double* M, const double* S) {
   HIPCHK(hipMemcpyAsync(c->f_M, M, D * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->f_S, S, D * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->ev_normc_ok = 0;
   return 0;
 }
 
@@ -641,6 +653,7 @@ int ddrl_observe_range(ddrl_ctx* c, const float* obs, int e0, int e1) {
   RouteArgs ra = c->route;
   ra.N = n;
   ra.e0 = e0;
+  c->ev_normc_ok = 0;
   launch_filter_push(c->stream, obs_r, n, g.obs_full_dim, c->f_n, c->f_M, c->f_S, c->f_normc,
                      g.filter_update, g.filter_enabled, c->f_dn, c->f_dM, c->f_dS, c->f_part);
   const float clip = g.filter_enabled ? g.filter_clip : 0.f;
@@ -702,23 +715,13 @@ int ddrl_bootstrap(ddrl_ctx* c) {
   return launch_act(c, make_act(c, 0, nullptr, nullptr, 1));
 }
 
-int ddrl_reward(ddrl_ctx* c, int t, const float* fw, const float* cfrc, const float* actions,
-                const uint8_t* done) {
-  CHK_CTX(c);
-  return ddrl_reward_range(c, t, 0, c->cfg.n_envs, fw, cfrc, actions, done);
-}
-
-int ddrl_reward_range(ddrl_ctx* c, int t, int e0, int e1, const float* fw, const float* cfrc, const float* actions,
-                      const uint8_t* done) {
-  CHK_CTX(c);
-  if (t < 0 || t >= c->cfg.frag_len) return fail("t out of range");
-  if (!fw || !cfrc || !actions) return fail("null reward input");
-  if (check_range(c, e0, e1)) return -1;
+// the reward tables of the context (record pointers included; env range and t by the caller)
+static RewardArgs make_reward(ddrl_ctx* c) {
   const ddrl_cfg& g = c->cfg;
   RewardArgs ra{};
   ra.P = g.n_policies; ra.N = g.n_envs; ra.n_agents = g.n_agents; ra.mode = g.reward_mode;
-  ra.e0 = e0; ra.n = e1 - e0;
-  ra.ctrl_w = g.ctrl_cost_weight; ra.contact_w = g.contact_cost_weight; ra.t = t;
+  ra.e0 = 0; ra.n = g.n_envs;
+  ra.ctrl_w = g.ctrl_cost_weight; ra.contact_w = g.contact_cost_weight;
   for (int p = 0; p < g.n_policies; ++p) {
     ra.k[p] = c->pol[p].k; ra.rec[p] = c->pol[p].rec; ra.lay[p] = c->pol[p].lay;
     for (int s = 0; s < c->pol[p].k; ++s) {
@@ -735,6 +738,24 @@ int ddrl_reward_range(ddrl_ctx* c, int t, int e0, int e1, const float* fw, const
       ra.contact_weight[j][b] = g.contact_weight[j][b];
     }
   }
+  return ra;
+}
+
+int ddrl_reward(ddrl_ctx* c, int t, const float* fw, const float* cfrc, const float* actions,
+                const uint8_t* done) {
+  CHK_CTX(c);
+  return ddrl_reward_range(c, t, 0, c->cfg.n_envs, fw, cfrc, actions, done);
+}
+
+int ddrl_reward_range(ddrl_ctx* c, int t, int e0, int e1, const float* fw, const float* cfrc, const float* actions,
+                      const uint8_t* done) {
+  CHK_CTX(c);
+  if (t < 0 || t >= c->cfg.frag_len) return fail("t out of range");
+  if (!fw || !cfrc || !actions) return fail("null reward input");
+  if (check_range(c, e0, e1)) return -1;
+  RewardArgs ra = make_reward(c);
+  ra.e0 = e0; ra.n = e1 - e0;
+  ra.t = t;
   launch_reward(c->stream, ra, fw, cfrc, actions, done, c->done_tn);
   HIPCHK(hipGetLastError());
   return 0;
@@ -892,6 +913,163 @@ int ddrl_rollout_hostenv(ddrl_ctx* c, ddrl_hostenv* env, int groups, const float
   // the pinned buffers are the caller's again only once the stream has consumed them
   if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("stream synchronize failed");
   for (auto& e : ev) (void)hipEventDestroy(e);
+  return rc ? -1 : 0;
+}
+
+// ---- evaluation (eval.hip) -----------------------------------------------------------
+// Whole episodes of the context's policies, N envs x E episodes each.  Nothing here writes a
+// record, done_tn, last_v, a per-policy filter, Adam state or a parameter.
+#define CHK_EVAL(c)                                    \
+  do {                                                 \
+    CHK_CTX(c);                                        \
+    if (!(c)->ev_on) return fail("evaluation: call ddrl_eval_begin first"); \
+  } while (0)
+
+int ddrl_eval_begin(ddrl_ctx* c, const ddrl_eval_cfg* ec) {
+  CHK_CTX(c);
+  if (!ec) return fail("null evaluation config");
+  if (c->cfg.model_kind != DDRL_MODEL_FFN) return fail("evaluation: fcnet models only");
+  if (ec->episodes_per_env < 1) return fail("evaluation: episodes_per_env must be >= 1");
+  if (ec->ctrl_roll < 0 || ec->ctrl_roll > 7) return fail("evaluation: ctrl_roll must be in [0, 7]");
+  if (!(ec->total_mass > 0.0)) return fail("evaluation: total_mass must be > 0");
+  const size_t N = c->cfg.n_envs, E = ec->episodes_per_env;
+  HIPCHK(hipStreamSynchronize(c->stream));   // nothing in flight reads a table that is replaced
+  if (!c->ev_acc) {
+    if (dalloc(c, &c->ev_acc, N * 4) || dalloc(c, &c->ev_count, N) || dalloc(c, &c->ev_ctr, 2) ||
+        dalloc(c, &c->ev_kin, N * 9))
+      return -1;
+  }
+  if ((int)E > c->ev_table_E) {
+    dfree(c, &c->ev_table);
+    c->ev_table_E = 0;
+    if (dalloc(c, &c->ev_table, N * E * 6)) return -1;
+    c->ev_table_E = (int)E;
+  }
+  HIPCHK(hipMemsetAsync(c->ev_acc, 0, N * 4 * 8, c->stream));
+  HIPCHK(hipMemsetAsync(c->ev_count, 0, N * 4, c->stream));
+  HIPCHK(hipMemsetAsync(c->ev_ctr, 0, 2 * 8, c->stream));
+  HIPCHK(hipMemsetAsync(c->ev_table, 0xFF, N * E * 6 * 8, c->stream));   // all-ones doubles: NaN rows
+  c->ev_cfg = *ec;
+  c->ev_normc_ok = 0;
+  c->ev_on = 1;
+  return 0;
+}
+
+int ddrl_eval_act(ddrl_ctx* c, const float* obs, const float* eps, float* actions, float* const* logits_out) {
+  CHK_EVAL(c);
+  if (!obs || !actions) return fail("null observation / actions buffer");
+  const ddrl_cfg& g = c->cfg;
+  const int N = g.n_envs;
+  const int push = g.filter_enabled && c->ev_cfg.filter_update;
+  const float clip = g.filter_enabled ? g.filter_clip : 0.f;
+  // the normalization constants are rewritten only when a push changes them, or when this is
+  // the first step since something else (eval_begin, filter_set, observe) may have
+  if (push || !c->ev_normc_ok) {
+    launch_filter_push(c->stream, obs, N, g.obs_full_dim, c->f_n, c->f_M, c->f_S, c->f_normc, c->ev_cfg.filter_update,
+                       g.filter_enabled, c->f_dn, c->f_dM, c->f_dS, c->f_part);
+    // RLlib compute_action filters with update=False: constants only, the statistics stay
+    if (g.policy_filter) launch_policy_filter(c->stream, c->route, obs, c->f_normc, clip, c->zs, c->pf, 0);
+    c->ev_normc_ok = !push;
+  }
+  EvalActArgs ea{};
+  for (int p = 0; p < g.n_policies; ++p) {
+    const Policy& P = c->pol[p];
+    ea.theta[p] = P.theta;
+    ea.cup[p] = g.leg_coupling ? P.theta + ffn_param_count(P.d, g.act_dim) : nullptr;
+    ea.logits_out[p] = logits_out ? logits_out[p] : nullptr;
+  }
+  ea.obs = obs; ea.normc = c->f_normc; ea.pf = g.policy_filter ? c->pf : nullptr; ea.clip = clip;
+  ea.eps = eps; ea.actions = actions;
+  ea.fc = FilterCount{c->f_n, c->f_dn, push ? N : 0};
+  RouteArgs ra = c->route;
+  ra.e0 = 0;
+  launch_eval_act(c->stream, ra, ea);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ddrl_eval_step(ddrl_ctx* c, const float* fw, const float* cfrc, const float* actions, const float* kin,
+                   const uint8_t* done) {
+  CHK_EVAL(c);
+  if (!fw || !cfrc || !actions || !kin || !done) return fail("null evaluation step input");
+  RewardArgs ra = make_reward(c);
+  for (int p = 0; p < DDRL_MAXP; ++p) ra.rec[p] = nullptr;   // the accumulator writes no record
+  EvalAccumArgs ev{};
+  ev.acc = c->ev_acc; ev.ep_count = c->ev_count; ev.table = c->ev_table; ev.counters = c->ev_ctr;
+  ev.E = c->ev_cfg.episodes_per_env; ev.ctrl_roll = c->ev_cfg.ctrl_roll; ev.total_mass = c->ev_cfg.total_mass;
+  launch_eval_accum(c->stream, ra, ev, fw, cfrc, actions, kin, done);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ddrl_eval_progress(ddrl_ctx* c, int64_t* episodes_done, int64_t* envs_finished) {
+  CHK_EVAL(c);
+  if (!episodes_done || !envs_finished) return fail("null progress output");
+  unsigned long long ctr[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(ctr, c->ev_ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipGetLastError());
+  if (check_err(c)) return -1;
+  *episodes_done = (int64_t)ctr[0];
+  *envs_finished = (int64_t)ctr[1];
+  return 0;
+}
+
+int ddrl_eval_results(ddrl_ctx* c, double* host, size_t n_rows) {
+  CHK_EVAL(c);
+  if (!host) return fail("null results buffer");
+  const size_t rows = (size_t)c->cfg.n_envs * c->ev_cfg.episodes_per_env;
+  if (n_rows != rows) return fail("evaluation: the result table has n_envs * episodes_per_env rows");
+  HIPCHK(hipMemcpyAsync(host, c->ev_table, rows * 6 * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int ddrl_eval_end(ddrl_ctx* c) {
+  CHK_EVAL(c);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->ev_on = 0;
+  return 0;
+}
+
+int ddrl_eval_hostenv(ddrl_ctx* c, ddrl_hostenv* env, const float* eps_dev, int eps_steps, int max_steps,
+                      int poll_every, int* steps_run) {
+  CHK_EVAL(c);
+  const ddrl_cfg& g = c->cfg;
+  if (!env) return fail("null host env");
+  if (env->N != g.n_envs || env->D != g.obs_full_dim) return fail("host env shape differs from the context's");
+  if (max_steps < 1 || poll_every < 1) return fail("evaluation: max_steps and poll_every must be >= 1");
+  if (eps_dev && eps_steps < 1) return fail("evaluation: eps_steps must be >= 1 with a noise buffer");
+  const size_t N = g.n_envs, D = g.obs_full_dim;
+  const size_t eps_step = N * g.n_agents * g.act_dim;
+  const int limit = eps_dev ? std::min(max_steps, eps_steps) : max_steps;
+  auto h2d = [&](void* dst, const void* src, size_t bytes) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : fail("H2D copy failed");
+  };
+  env->reset_episodes();
+  int rc = h2d(c->h_obs, env->obs, N * D * 4);
+  int t = 0;
+  for (; t < limit && !rc;) {
+    rc = ddrl_eval_act(c, c->h_obs, eps_dev ? eps_dev + (size_t)t * eps_step : nullptr, c->h_act, nullptr);
+    if (!rc && hipMemcpyAsync(env->act, c->h_act, N * 8 * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+      rc = fail("D2H copy failed");
+    // the actions are on the host, and the previous step's H2D copies have left the pinned buffers
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail("stream synchronize failed");
+    if (rc) break;
+    env->step(0, (int)N);
+    rc = h2d(c->h_fw, env->fw, N * 4) || h2d(c->h_cfrc, env->cfrc, N * 84 * 4) || h2d(c->h_done, env->done, N) ||
+         h2d(c->ev_kin, env->kin, N * 9 * 4) || h2d(c->h_obs, env->obs, N * D * 4) ||
+         ddrl_eval_step(c, c->h_fw, c->h_cfrc, c->h_act, c->ev_kin, c->h_done);
+    ++t;
+    if (!rc && t % poll_every == 0) {
+      int64_t eps_done = 0, fin = 0;
+      rc = ddrl_eval_progress(c, &eps_done, &fin);
+      if (!rc && fin == (int64_t)N) break;
+    }
+  }
+  // the pinned buffers are the caller's again only once the stream has consumed them
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("stream synchronize failed");
+  if (steps_run) *steps_run = t;
   return rc ? -1 : 0;
 }
 

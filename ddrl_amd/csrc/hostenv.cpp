@@ -100,7 +100,6 @@ namespace {
 constexpr double kH = 0.01;           // integration step; frame_skip 5 -> 0.05 s per env step
 constexpr int kFrameSkip = 5;
 constexpr double kDt = kH * kFrameSkip;
-constexpr int kTimeLimit = 1000;      // gym TimeLimit of the registered envs (simulation_envs/__init__.py:27-32)
 constexpr double kQ0[8] = {0.0, 1.0, 0.0, -1.0, 0.0, -1.0, 0.0, 1.0};   // rest pose (knees bent)
 constexpr double kGear = 30.0, kSpring = 8.0, kDamp = 1.5, kLimit = 1.4;
 constexpr double kShin = 0.7, kHipOff = 0.08, kGround = 400.0, kGroundDamp = 8.0;
@@ -217,8 +216,11 @@ void ddrl_hostenv::step_env(int e, const float* a8) {
     foot[5] = (float)f;
     cf[1 * 6 + 5] += (float)(0.05 * f);
   }
+  float* kn = kin + (size_t)e * 9;
+  kn[0] = (float)(s.x - x0);
+  for (int j = 0; j < 8; ++j) kn[1 + j] = (float)s.qd[j];
   const bool unhealthy = !(s.z > 0.1 && s.z < 1.5) || !std::isfinite(s.z);
-  const bool d = unhealthy || s.steps >= kTimeLimit;
+  const bool d = unhealthy || s.steps >= time_limit;
   done[e] = d ? 1 : 0;
   if (d) {
     reset_env(e);
@@ -234,7 +236,7 @@ void ddrl_hostenv::reset_all() {
       st[e].episode = 0;
       reset_env(e);
       // staggered episode phases, like a long-running sampler (the synthetic rollouts too)
-      st[e].steps = (int)(((uint64_t)e * 2654435761ull + seed) % kTimeLimit);
+      st[e].steps = (int)(((uint64_t)e * 2654435761ull + seed) % time_limit);
       write_obs(e, nullptr);
       done[e] = 0;
     }
@@ -244,6 +246,16 @@ void ddrl_hostenv::reset_all() {
 void ddrl_hostenv::reset_state() {
   pool->parallel_for(N, [this](int lo, int hi) {
     for (int e = lo; e < hi; ++e) reset_env(e, false);   // steps = 0: the TimeLimit count restarts too
+  });
+}
+
+void ddrl_hostenv::reset_episodes() {
+  pool->parallel_for(N, [this](int lo, int hi) {
+    for (int e = lo; e < hi; ++e) {
+      reset_env(e);
+      write_obs(e, nullptr);
+      done[e] = 0;
+    }
   });
 }
 
@@ -286,12 +298,13 @@ extern "C" int ddrl_hostenv_create(int n_envs, int obs_dim, int n_threads, uint6
     return *p != nullptr;
   };
   if (!alloc((void**)&h->obs, N * obs_dim * 4) || !alloc((void**)&h->act, N * 8 * 4) || !alloc((void**)&h->fw, N * 4) ||
-      !alloc((void**)&h->cfrc, N * 14 * 6 * 4) || !alloc((void**)&h->done, N)) {
+      !alloc((void**)&h->cfrc, N * 14 * 6 * 4) || !alloc((void**)&h->done, N) || !alloc((void**)&h->kin, N * 9 * 4)) {
     g_henv_err = "ddrl_hostenv_create: host buffer allocation failed";
     ddrl_hostenv_destroy(h);
     return -1;
   }
   std::memset(h->act, 0, N * 8 * 4);
+  std::memset(h->kin, 0, N * 9 * 4);
   h->pool = new hostenv::Pool(n_threads);
   *out = h;
   return 0;
@@ -300,7 +313,7 @@ extern "C" int ddrl_hostenv_create(int n_envs, int obs_dim, int n_threads, uint6
 extern "C" int ddrl_hostenv_destroy(ddrl_hostenv* h) {
   if (!h) return 0;
   delete h->pool;
-  for (void* p : {(void*)h->obs, (void*)h->act, (void*)h->fw, (void*)h->cfrc, (void*)h->done}) {
+  for (void* p : {(void*)h->obs, (void*)h->act, (void*)h->fw, (void*)h->cfrc, (void*)h->done, (void*)h->kin}) {
     if (!p) continue;
     if (h->pinned) (void)hipHostFree(p);
     else std::free(p);
@@ -374,5 +387,32 @@ extern "C" int ddrl_hostenv_reset_state(ddrl_hostenv* h) {
     return -1;
   }
   h->reset_state();
+  return 0;
+}
+
+extern "C" int ddrl_hostenv_kin(ddrl_hostenv* h, float** kin) {
+  if (!h || !kin) {
+    g_henv_err = "ddrl_hostenv_kin: null host env / output pointer";
+    return -1;
+  }
+  *kin = h->kin;
+  return 0;
+}
+
+extern "C" int ddrl_hostenv_set_time_limit(ddrl_hostenv* h, int steps) {
+  if (!h || steps < 1) {
+    g_henv_err = "ddrl_hostenv_set_time_limit: a host env and steps >= 1";
+    return -1;
+  }
+  h->time_limit = steps;
+  return 0;
+}
+
+extern "C" int ddrl_hostenv_reset_episodes(ddrl_hostenv* h) {
+  if (!h) {
+    g_henv_err = "null host env";
+    return -1;
+  }
+  h->reset_episodes();
   return 0;
 }

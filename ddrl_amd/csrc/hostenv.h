@@ -69,6 +69,10 @@ struct ddrl_hostenv {
   // pinned host buffers (hipHostMalloc): obs [N][D], act [N][8], fw [N], cfrc [N][14][6], done [N]
   float *obs = nullptr, *act = nullptr, *fw = nullptr, *cfrc = nullptr;
   uint8_t* done = nullptr;
+  // kin [N][9]: {torso dx of the step, joint velocities qd[0..7]} as the step left them, written
+  // before a done env is reset (evaluation's distance and power need the episode's last step)
+  float* kin = nullptr;
+  int time_limit = 1000;   // gym TimeLimit of the registered envs (simulation_envs/__init__.py:27-32)
   bool pinned = false;
   hostenv::Pool* pool = nullptr;
 
@@ -82,6 +86,9 @@ struct ddrl_hostenv {
   // reset() re-draws it), no done flag is raised and the observation buffer is not rewritten
   // (the adaptor discards env.reset()'s observation; the sampler acts on the last one it has)
   void reset_state();
+  // evaluation: every env starts a fresh episode at step 0 (no staggered phases): target
+  // velocity drawn, observation written, done cleared
+  void reset_episodes();
   // step the envs [e0, e1) with the actions act[e][8]; writes obs / fw / cfrc / done of the range
   void step(int e0, int e1);
 };

@@ -101,6 +101,32 @@ struct RewardArgs {
 void launch_reward(hipStream_t s, const RewardArgs& ra, const float* fw, const float* cfrc,
                    const float* actions, const uint8_t* done, uint8_t* done_tn);
 
+// ---- evaluation (eval.hip): fused observe + forward + action, episode statistics ----
+struct EvalActArgs {
+  const float* theta[DDRL_MAXP];
+  const float* cup[DDRL_MAXP];     // "cup" leg-coupling table [4][A] (nullptr: none)
+  float* logits_out[DDRL_MAXP];    // optional [C_p][2A] logits of this step (nullptr: not written)
+  const float* obs;                // raw observations [N][full_dim]
+  const double* normc;             // env-side filter constants (mean, std + 1e-8) per column
+  const double* pf;                // per-policy filter state (PF_* layout) or nullptr
+  float clip;
+  const float* eps;                // [N][n_agents][A]; nullptr: deterministic (the mean)
+  float* actions;                  // [N][8]
+  FilterCount fc;                  // batch count of this step's env-side filter push (0: none)
+};
+void launch_eval_act(hipStream_t s, const RouteArgs& ra, const EvalActArgs& ea);
+struct EvalAccumArgs {
+  double* acc;                     // [N][4]: return, power, distance, steps of the running episode
+  int32_t* ep_count;               // [N] episodes recorded per env
+  double* table;                   // [N][E][6]: return, steps, distance, power, velocity, CoT
+  unsigned long long* counters;    // [2]: episodes recorded, envs that filled their quota
+  int E, ctrl_roll;
+  double total_mass;
+};
+// ra: the reward tables of launch_reward (rec / lay / t unused); kin[N][9] = {dx, joint qvel[8]}
+void launch_eval_accum(hipStream_t s, const RewardArgs& ra, const EvalAccumArgs& ev, const float* fw,
+                       const float* cfrc, const float* actions, const float* kin, const uint8_t* done);
+
 // ---- GAE + standardization statistics ----
 struct GaeArgs {
   float* rec; RecLayout lay; int C, T, N, k;

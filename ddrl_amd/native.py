@@ -45,6 +45,15 @@ class DdrlCfg(C.Structure):
     ]
 
 
+class DdrlEvalCfg(C.Structure):
+    """ddrl_eval_cfg; the defaults are the reference's (evaluation/rollout_episodes.py:146, :152)."""
+    _fields_ = [("episodes_per_env", i32), ("filter_update", i32), ("ctrl_roll", i32), ("reserved", i32),
+                ("total_mass", C.c_double)]
+
+
+TOTAL_MASS = 8.78710174560547   # mj_getTotalmass of the QuAntruped model (rollout_episodes.py:152)
+EVAL_COLUMNS = ("reward", "steps", "distance", "power", "velocity", "cot")
+
 VP = C.c_void_p
 _SIGS = {
     "ddrl_abi_version": ([], C.c_int),
@@ -116,6 +125,16 @@ _SIGS = {
     "ddrl_hostenv_target_velocities": ([VP, C.POINTER(C.c_float), C.c_int], C.c_int),
     "ddrl_hostenv_reset_state": ([VP], C.c_int),
     "ddrl_rollout_hostenv": ([VP, VP, C.c_int, VP, C.c_int], C.c_int),
+    "ddrl_hostenv_kin": ([VP, C.POINTER(VP)], C.c_int),
+    "ddrl_hostenv_set_time_limit": ([VP, C.c_int], C.c_int),
+    "ddrl_hostenv_reset_episodes": ([VP], C.c_int),
+    "ddrl_eval_begin": ([VP, C.POINTER(DdrlEvalCfg)], C.c_int),
+    "ddrl_eval_act": ([VP, VP, VP, VP, C.POINTER(VP)], C.c_int),
+    "ddrl_eval_step": ([VP, VP, VP, VP, VP, VP], C.c_int),
+    "ddrl_eval_progress": ([VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+    "ddrl_eval_results": ([VP, VP, C.c_size_t], C.c_int),
+    "ddrl_eval_end": ([VP], C.c_int),
+    "ddrl_eval_hostenv": ([VP, VP, VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
 }
 
 _lib = None
@@ -458,6 +477,47 @@ class Context:
         """A fragment with the envs stepped on the host (HostEnv), pipelined over env groups."""
         _ck(self.lib.ddrl_rollout_hostenv(self.h, env.h, groups, _ptr(eps_dev), 1 if reset else 0))
 
+    # ---- evaluation (whole episodes, N envs x E episodes each; fcnet models) ----
+    def eval_begin(self, episodes_per_env, filter_update=False, ctrl_roll=2, total_mass=TOTAL_MASS):
+        ec = DdrlEvalCfg(int(episodes_per_env), 1 if filter_update else 0, int(ctrl_roll), 0, float(total_mass))
+        _ck(self.lib.ddrl_eval_begin(self.h, C.byref(ec)))
+        self.eval_episodes = int(episodes_per_env)
+
+    def eval_act(self, obs_dev, eps_dev, actions_dev, logits_out=None):
+        """One fused launch from the raw observations to the env actions; eps_dev None takes the
+        mean (explore=False).  logits_out: per policy a device buffer [C_p][2A] or None."""
+        lo = None
+        if logits_out is not None:
+            lo = (VP * MAX_P)(*[_ptr(logits_out[p]) if p < len(logits_out) else None for p in range(MAX_P)])
+        _ck(self.lib.ddrl_eval_act(self.h, _ptr(obs_dev), _ptr(eps_dev), _ptr(actions_dev), lo))
+
+    def eval_step(self, fw_dev, cfrc_dev, actions_dev, kin_dev, done_dev):
+        _ck(self.lib.ddrl_eval_step(self.h, _ptr(fw_dev), _ptr(cfrc_dev), _ptr(actions_dev), _ptr(kin_dev),
+                                    _ptr(done_dev)))
+
+    def eval_progress(self):
+        """(rows written so far, envs that have filled their quota); synchronizes."""
+        a, b = C.c_int64(), C.c_int64()
+        _ck(self.lib.ddrl_eval_progress(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def eval_results(self):
+        """float64 [N, E, 6] (EVAL_COLUMNS); rows of episodes that did not finish are NaN."""
+        E = getattr(self, "eval_episodes", 0)
+        a = np.empty((self.cfg.n_envs, E, 6), np.float64)
+        _ck(self.lib.ddrl_eval_results(self.h, a.ctypes.data, self.cfg.n_envs * E))
+        return a
+
+    def eval_end(self):
+        _ck(self.lib.ddrl_eval_end(self.h))
+
+    def eval_hostenv(self, env, eps_dev=None, eps_steps=0, max_steps=1000, poll_every=25):
+        """The whole evaluation over a HostEnv, loop in C++; returns the env steps taken."""
+        n = C.c_int()
+        _ck(self.lib.ddrl_eval_hostenv(self.h, env.h, _ptr(eps_dev), int(eps_steps), int(max_steps), int(poll_every),
+                                       C.byref(n)))
+        return int(n.value)
+
     def policy_forward(self, pid, obs_dev, n, logits_dev, values_dev, node_dev=None):
         _ck(self.lib.ddrl_policy_forward(self.h, pid, _ptr(obs_dev), _ptr(node_dev), n,
                                          _ptr(logits_dev), _ptr(values_dev)))
@@ -492,6 +552,9 @@ class HostEnv:
         self.cfrc = view(ptrs[3], C.c_float, (n_envs, 14, 6))
         self.done = view(ptrs[4], C.c_uint8, (n_envs,))
         self.threads = self.lib.ddrl_hostenv_threads(h)
+        kp = VP()
+        self._ck(self.lib.ddrl_hostenv_kin(h, C.byref(kp)))
+        self.kin = view(kp, C.c_float, (n_envs, 9))   # {dx, joint qvel[8]} of the step, pre-reset
 
     def _ck(self, rc):
         if rc != 0:
@@ -519,6 +582,18 @@ class HostEnv:
         self._live()
         self._ck(self.lib.ddrl_hostenv_reset_state(self.h))
 
+    def set_time_limit(self, steps):
+        """The TimeLimit of every env (default 1000): an episode ends after `steps` steps."""
+        self._live()
+        self._ck(self.lib.ddrl_hostenv_set_time_limit(self.h, int(steps)))
+
+    def reset_episodes(self):
+        """Every env starts a fresh episode at step 0 (reset() staggers the episode phases);
+        returns a copy of the observations."""
+        self._live()
+        self._ck(self.lib.ddrl_hostenv_reset_episodes(self.h))
+        return self.obs.copy()
+
     @property
     def target_velocities(self):
         """Each env's current target velocity (the draw of its current episode)."""
@@ -532,7 +607,7 @@ class HostEnv:
         so no attribute of this object can read freed memory afterwards; copies made by the
         caller stay valid."""
         if getattr(self, "h", None):
-            self.obs = self.act = self.fw = self.cfrc = self.done = None
+            self.obs = self.act = self.fw = self.cfrc = self.done = self.kin = None
             self.lib.ddrl_hostenv_destroy(self.h)
             self.h = None
 

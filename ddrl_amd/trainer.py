@@ -460,7 +460,123 @@ class PPOTrainer:
         self._after_load(learner)
         return list(self.policy_ids)
 
+    # -- evaluation ----------------------------------------------------------------------
+    def _eval_context(self, n_envs, env_config=None):
+        """A separate context of n_envs envs (cached per shape) holding a copy of the current
+        weights and per-policy filters; the training context is only read."""
+        cache = self.__dict__.setdefault("_eval_ctx", {})
+        key = (int(n_envs), json.dumps(env_config, sort_keys=True))
+        if key not in cache:
+            config = self.config if env_config is None else {
+                **self.config, "env_config": {**self.config.get("env_config", {}), **env_config}}
+            cfg, _ = make_cfg(self.config["env"], n_envs, 1, config)
+            cache[key] = N.Context(cfg, self.device.index, self.stream.cuda_stream)
+        ectx = cache[key]
+        for p in range(self.cfg.n_policies):
+            ectx.params_set(p, self.ctx.params_get(p))
+            if self.cfg.policy_filter:
+                ectx.policy_filter_set(p, *self.ctx.policy_filter_get(p))
+        return ectx
+
+    def evaluate(self, num_episodes=100, num_steps=1000, explore=True, tvel=None, n_envs=None,
+                 env_filter="continue", seed=0):
+        """Run the current policies for whole episodes over the host env plane and return the
+        reference's tuple (reward_eps, steps_eps, dist_eps, power_total_eps, vel_eps, cot_eps) of
+        evaluation/rollout_episodes.py:26-164, one entry per episode.
+
+        n_envs (default min(num_episodes, 128)) envs run E = ceil(num_episodes / n_envs) episodes
+        each, side by side, instead of the reference's sequential episodes; the result is the first
+        num_episodes completed rows in env-major order.  A fixed quota per env keeps short episodes
+        from being over-represented.  num_steps is the episode length limit (:83).
+
+        explore=True is the default because the reference calls compute_action without `explore`
+        (:103-107), so RLlib samples from the action distribution; explore=False takes the mean.
+        tvel: a one-entry target-velocity list (:38-39).  env_filter: the env-side MeanStdFilter
+        of the evaluation -- "continue": a copy of the training filter that keeps updating (the
+        reference's singleton does, quantruped_adaptor_multi_environment.py:83-85), "frozen": the
+        copy, not updated, "fresh": a new filter, updating (what the reference's separate
+        evaluation process gets).  The per-policy filters are applied without updates, as RLlib's
+        compute_action does.  The training context, its env backend and the noise generator are
+        not touched: evaluation runs on its own context, env plane and generator (`seed`)."""
+        if env_filter not in ("continue", "frozen", "fresh"):
+            raise ValueError(f"env_filter {env_filter!r}: 'continue', 'frozen' or 'fresh'")
+        if self.cfg.model_kind != N.MODEL_FFN:
+            raise N.DdrlError("evaluation: fcnet models only")
+        torch, cfg = self.torch, self.cfg
+        num_episodes, num_steps = int(num_episodes), int(num_steps)
+        if num_episodes < 1 or num_steps < 1:
+            raise ValueError("num_episodes and num_steps must be >= 1")
+        n_envs = int(n_envs or min(num_episodes, 128))
+        E = -(-num_episodes // n_envs)
+        ectx = self._eval_context(n_envs)
+        D = cfg.obs_full_dim
+        if env_filter == "fresh":
+            ectx.filter_set(0.0, np.zeros(D), np.zeros(D))
+        else:
+            ectx.filter_set(*self.rctx.filter_get())
+        tv = [float(tvel)] if tvel else [float(v) for v in (self.env.target_velocity_list or [0.0])]
+        henv = N.HostEnv(n_envs, D, n_threads=int(self.config.get("num_host_threads", 4)), seed=seed,
+                         target_velocity=tv if len(tv) > 1 else tv[0])
+        try:
+            henv.set_time_limit(num_steps)
+            max_steps = E * num_steps   # every env has had E episodes by then
+            eps = None
+            if explore:
+                gen = torch.Generator(device=self.device)
+                gen.manual_seed(seed + 1)
+                eps = torch.randn((max_steps, n_envs, cfg.n_agents, cfg.act_dim), device=self.device, generator=gen)
+            ectx.eval_begin(E, filter_update=env_filter != "frozen")
+            ectx.eval_hostenv(henv, eps, max_steps if explore else 0, max_steps, poll_every=min(25, num_steps))
+            rows = ectx.eval_results().reshape(-1, 6)
+            ectx.eval_end()
+        finally:
+            henv.close()
+        rows = rows[~np.isnan(rows[:, 1])][:num_episodes]
+        reward, steps, dist, power, vel, cot = (rows[:, i].tolist() for i in range(6))
+        return reward, [int(s) for s in steps], dist, power, vel, cot
+
+    def compute_action(self, obs, policy_id=None, explore=None, seed=None, agent_id=None):
+        """Trainer.compute_action for one agent observation (the policy's input row, as the env
+        adaptor hands it out): the per-policy filter without update, the policy forward and the
+        action, clipped to [-1, 1] (clip_actions).  explore None / True samples (RLlib's default),
+        False takes the mean.  Runs through ddrl_eval_act on a one-env context whose env-side
+        filter is off, with the row placed at the agent's columns of a full observation.
+        agent_id (default: the policy's first agent) selects the leg row of the "cup" model."""
+        policy_id = self.policy_ids[0] if policy_id is None else policy_id
+        p = self.policy_ids.index(policy_id)
+        cfg, torch = self.cfg, self.torch
+        A, d = cfg.act_dim, int(cfg.obs_dim[p])
+        obs = np.asarray(obs, np.float32).reshape(-1)
+        if obs.size != d:
+            raise ValueError(f"{policy_id}: observation of {obs.size} values, the policy takes {d}")
+        ectx = self._eval_context(1, {"observation_filter_env": False})
+        agents = [j for j in range(cfg.n_agents) if cfg.agent_policy[j] == p]
+        j = agents[0] if agent_id is None else list(self.env.agent_names).index(agent_id)
+        if j not in agents:
+            raise ValueError(f"agent {agent_id!r} is not mapped to policy {policy_id!r}")
+        full = np.zeros((1, cfg.obs_full_dim), np.float32)
+        for f in range(d):
+            i = ectx.cfg.obs_index[j][f]
+            if i >= 0:
+                full[0, i] = obs[f]
+        dev = lambda a: torch.from_numpy(a).to(self.device)
+        logits = [torch.zeros((len([a for a in range(cfg.n_agents) if cfg.agent_policy[a] == q]), 2 * A),
+                              dtype=torch.float32, device=self.device) for q in range(cfg.n_policies)]
+        actions = torch.zeros((1, 8), dtype=torch.float32, device=self.device)
+        ectx.eval_begin(1)
+        ectx.eval_act(dev(full), None, actions, logits)
+        ectx.synchronize()
+        ectx.eval_end()
+        lg = logits[p][agents.index(j)].cpu().numpy()
+        act = lg[:A].copy()
+        if explore is None or explore:
+            rng = np.random.default_rng(seed)
+            act = act + np.exp(lg[A:]) * rng.standard_normal(A).astype(np.float32)
+        return np.clip(act, -1.0, 1.0).astype(np.float32)
+
     def stop(self):
+        for ectx in self.__dict__.pop("_eval_ctx", {}).values():
+            ectx.close()
         if self.rctx is not self.ctx:
             self.rctx.close()
         self.ctx.close()

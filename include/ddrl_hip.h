@@ -207,6 +207,58 @@ int ddrl_hostenv_target_velocities(ddrl_hostenv* env, float* out, int n_envs);
  * The terrain regeneration of the same hook is MuJoCo-side (out of scope). */
 int ddrl_hostenv_reset_state(ddrl_hostenv* env);
 int ddrl_rollout_hostenv(ddrl_ctx* ctx, ddrl_hostenv* env, int groups, const float* eps_dev, int reset);
+/* What evaluation needs of the env plane.
+ *   kin: the pinned buffer kin[N][9] = {torso dx of the step, joint velocities qd[0..7]}, written
+ *     by step before a done env is reset (the observation of a done step is the reset one);
+ *   set_time_limit: the TimeLimit of every env (default 1000), the reference's
+ *     `while not done and steps < num_steps` (evaluation/rollout_episodes.py:83);
+ *   reset_episodes: every env starts a fresh episode at step 0 -- target velocity drawn,
+ *     observation written, done cleared (ddrl_hostenv_reset staggers the episode phases). */
+int ddrl_hostenv_kin(ddrl_hostenv* env, float** kin);
+int ddrl_hostenv_set_time_limit(ddrl_hostenv* env, int steps);
+int ddrl_hostenv_reset_episodes(ddrl_hostenv* env);
+
+/* Evaluation of the context's policies over whole episodes (evaluation/rollout_episodes.py:26-164):
+ * N envs x E episodes each instead of the reference's sequential episodes.  fcnet models only.
+ * Reads the weights, coupling table, routing tables and filters; writes no record, done flag,
+ * bootstrap value, per-policy filter, Adam state or parameter, and the env-side filter
+ * statistics only with filter_update.
+ *   eval_begin: allocates / clears the per-env accumulators and the result table [N][E][6]
+ *     (rows NaN until written);
+ *   eval_act:  one launch: env-side normalization, per-policy filter (read-only), routing,
+ *     policy forward and action of every agent from the raw observations obs_dev[N][obs_full_dim];
+ *     eps_dev[N][n_agents][A] samples mean + std * eps, NULL takes the mean (RLlib explore=False);
+ *     writes the clipped env actions actions_dev[N][8] and, when logits_out_dev (a host array of
+ *     n_policies device pointers, entries may be NULL) is given, the logits [C_p][2A] per policy;
+ *   eval_step: the env's answer to those actions -- fw_dev[N], cfrc_dev[N][14][6], the actions,
+ *     kin_dev[N][9] (ddrl_hostenv_kin's layout), done_dev[N] -- into the fp64 accumulators
+ *     {return, power, distance, steps}; a done env below its quota writes its row
+ *     {return, steps, distance, power, velocity = distance / steps,
+ *      CoT = (power / steps) / (total_mass * velocity)} and every done env restarts;
+ *   eval_progress: synchronizes; rows written so far and envs that have filled their quota;
+ *   eval_results: the table, n_rows = N * E rows of 6 doubles, env-major. */
+typedef struct ddrl_eval_cfg {
+  int32_t episodes_per_env;   /* E >= 1 */
+  int32_t filter_update;      /* env-side MeanStdFilter keeps pushing during evaluation */
+  int32_t ctrl_roll;          /* 2 in the reference (np.roll(ctrl, -2), rollout_episodes.py:146) */
+  int32_t reserved;
+  double total_mass;          /* 8.78710174560547 (rollout_episodes.py:152) */
+} ddrl_eval_cfg;
+int ddrl_eval_begin(ddrl_ctx* ctx, const ddrl_eval_cfg* cfg);
+int ddrl_eval_act(ddrl_ctx* ctx, const float* obs_dev, const float* eps_dev, float* actions_dev,
+                  float* const* logits_out_dev);
+int ddrl_eval_step(ddrl_ctx* ctx, const float* fw_dev, const float* cfrc_dev, const float* actions_dev,
+                   const float* kin_dev, const uint8_t* done_dev);
+int ddrl_eval_progress(ddrl_ctx* ctx, int64_t* episodes_done, int64_t* envs_finished);
+int ddrl_eval_results(ddrl_ctx* ctx, double* host, size_t n_rows);
+int ddrl_eval_end(ddrl_ctx* ctx);
+/* A whole evaluation over the host env plane, loop in C++: reset_episodes, then per step
+ * eval_act -> D2H actions -> host step -> H2D (obs, fw, cfrc, kin, done) -> eval_step, until every
+ * env has filled its quota (polled every poll_every steps) or max_steps steps ran.  eps_dev: NULL,
+ * or eps_steps steps of [N][n_agents][A] noise (the loop then stops at eps_steps at the latest).
+ * steps_run (may be NULL): env steps taken. */
+int ddrl_eval_hostenv(ddrl_ctx* ctx, ddrl_hostenv* env, const float* eps_dev, int eps_steps, int max_steps,
+                      int poll_every, int* steps_run);
 
 /* Postprocessing: GAE over the fragment for every policy + advantage standardization
  * statistics (a11/a12). */
