@@ -51,36 +51,22 @@
 #define GNI 5              // feature rows i per wave (ceil(19 / 4))
 
 enum { GNN_ACT = 0, GNN_FWD = 1, GNN_GRAD = 2 };
-// the wave index as a scalar and the wave's own h block loaded directly (A/B: -DDDRL_GNN_HW=0)
-#ifndef DDRL_GNN_HW
-#define DDRL_GNN_HW 1
-#endif
 // Gradient launches split each tile's backward over GNN_Z workgroups (blockIdx.z): all of
 // them run the forward (the backward needs every activation), workgroup z then computes only
 // the hypernetwork feature rows k % GNN_Z == z of each wave and its Wnode / Wmsg tile slots
 // (gnn_tile_owner); every partial is still written by exactly one workgroup.  Measured at C5
 // (2048 envs): Z = 1 / 2 / 4 / 5 -> 25.2 / 24.4 / 21.9 / 24.9 us per step (Z = 5 puts two
 // workgroups on some CUs: 320 > 256).
-#ifndef DDRL_GNN_Z
-#define DDRL_GNN_Z 4
-#endif
-constexpr int GNN_Z = DDRL_GNN_Z;
-static_assert(GNN_Z >= 1 && GNN_Z <= GNI, "split of the gradient backward");
-// Owner of the Wnode / Wmsg tile slot k (0..7) of each wave.  With four shares, share 0's
-// waves 0-2 also carry the hypernetwork rows 16-18 (19 rows over 16 waves), so its tile
-// slots go to shares 1-3 (measured 0.26 us per step shorter at C5 than k % 4).
-__device__ __forceinline__ int gnn_tile_owner(int k) {
-#ifdef DDRL_GNN_TILE_MOD
-  return k % GNN_Z;
-#endif
-  return GNN_Z == 4 ? 1 + k % 3 : k % GNN_Z;
-}
+constexpr int GNN_Z = 4;
+static_assert(GNN_Z <= GNI, "split of the gradient backward");
+// Owner of the Wnode / Wmsg tile slot k (0..7) of each wave.  Share 0's waves 0-2 also carry
+// the hypernetwork rows 16-18 (19 rows over 16 waves), so its tile slots go to shares 1-3
+// (measured 0.26 us per step shorter at C5 than k % 4).
+__device__ __forceinline__ int gnn_tile_owner(int k) { return 1 + k % 3; }
 // Owner of the hypernetwork backward's (feature row slot k, 16-column block t) of each wave:
-// row slot k % GNN_Z, except that with four shares the last slot (rows 16-18, waves 0-2) is
-// dealt by column block, so no wave carries two whole rows.
-__device__ __forceinline__ int gnn_hbwd_owner(int k, int t) {
-  return (GNN_Z == 4 && k == GNI - 1) ? t : k % GNN_Z;
-}
+// row slot k % GNN_Z, except that the last slot (rows 16-18, waves 0-2) is dealt by column
+// block, so no wave carries two whole rows.
+__device__ __forceinline__ int gnn_hbwd_owner(int k, int t) { return k == GNI - 1 ? t : k % GNN_Z; }
 
 // Layer kernels of a net, in the reference's variable order: "wmsg" holds MPNN msg_transform,
 // GCN linear, MPNN2 msg_transform [128][64] or GAT1 pre_att_linear; "wnode" holds MPNN
@@ -138,15 +124,12 @@ static_assert(2 * DDRL_LBLK + 256 <= 8 * 1024, "MPNN2 / GAT1 images inside the h
 // The one-launch step (l2: the partials are read by reducers on the same XCD in the same
 // launch, gnn_tail) keeps them in the XCD's L2 with plain stores instead.
 // (measured at C5, 2048 envs, one box: plain 18.19 us per step, nontemporal 18.58)
-#ifndef DDRL_GNN_L2_PLAIN
-#define DDRL_GNN_L2_PLAIN 1
-#endif
 __device__ __forceinline__ void pst(bool l2, float* p, float v) {
-  if (l2 && DDRL_GNN_L2_PLAIN) *p = v;
+  if (l2) *p = v;
   else __builtin_nontemporal_store(v, p);
 }
 __device__ __forceinline__ void pst4(bool l2, float* p, floatx4 v) {
-  if (l2 && DDRL_GNN_L2_PLAIN) *reinterpret_cast<floatx4*>(p) = v;
+  if (l2) *reinterpret_cast<floatx4*>(p) = v;
   else __builtin_nontemporal_store(v, reinterpret_cast<floatx4*>(p));
 }
 __device__ __forceinline__ float leaky02(float x) { return x > 0.f ? x : 0.2f * x; }   // tf.nn.leaky_relu
@@ -198,12 +181,8 @@ extern "C" int ddrl_diag_gnn_stamps(unsigned long long* host, unsigned long long
 template <int A, int MODE, int NET, int L>
 __device__ __forceinline__ void gnn_tile(const GnnArgs& ga, float* lds, const int tile, const int zs) {
   constexpr int O = NET ? 1 : 2 * A;
-#if DDRL_GNN_HW
   const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, q = lane >> 4,
             w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: scalar index arithmetic
-#else
-  const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, q = lane >> 4, w = tid >> 6;
-#endif
   const int g = c >> 2, n = c & 3;
   const int graph = 4 * tile + g;
   const bool gvalid = graph < ga.n_graphs;
@@ -359,13 +338,11 @@ __device__ __forceinline__ void gnn_tile(const GnnArgs& ga, float* lds, const in
   for (int fb = 0; fb < 4; ++fb)
 #pragma unroll
     for (int r = 0; r < 4; ++r) h[fb][r] = himg[wbase(r) + 16 * fb];
-#if DDRL_GNN_HW
   // this wave's own block h[w] (the backward's dtanh): read here, not indexed out of h[][] with
   // the wave index later (a select chain over every block, ~340 instructions)
   float hw[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) hw[r] = himg[wbase(r) + 16 * w];
-#endif
   GSTAMP(2);
 
   // ---- message-passing layer: output block w of y (lane: node c, features 16 w + 4 q + r) ----
@@ -560,42 +537,6 @@ __device__ __forceinline__ void gnn_tile(const GnnArgs& ga, float* lds, const in
     ga.statp[(NET * (DDRL_MB / 4) + tile) * 8 + tid] = s;
   }
   float* P = ga.part + (size_t)tile * ga.part_stride;
-#ifdef DDRL_ABL_GNN_FWD_HANDOFF
-  // Timing-only cost model (results wrong): one forward per tile shared by
-  // its GNN_Z backward shares through the XCD's L2.  Share 0 publishes 16 KB (the size of a net's
-  // dz / h / du / dm images for a tile) and a tagged flag in the padding of its partial row; the
-  // other shares wait for the flag and read the 16 KB back.  Every share still runs its own
-  // forward above: the forward is on the step's critical path either way (the shares wait for
-  // share 0's), so this build adds exactly the hand-off.  The payload lands in partial slots that
-  // the real partial stores overwrite later.
-  if (ga.tail) {
-    unsigned* hf = reinterpret_cast<unsigned*>(P + ga.n_params + NET);
-    if (zs == 0) {
-      for (int i = tid; i < 4096; i += 256) P[i] = lds[i];
-      __builtin_amdgcn_s_waitcnt(0);
-      __syncthreads();
-      if (tid == 0) __hip_atomic_store(hf, ga.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      if (tid == 0) {
-        const unsigned long long h0 = __builtin_amdgcn_s_memrealtime();
-        while (__hip_atomic_load(hf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ga.tag) {
-          if (__builtin_amdgcn_s_memrealtime() - h0 > 300000000ull) {
-            __hip_atomic_store(ga.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-      }
-      __syncthreads();
-      float acc = 0.f;
-      for (int i = tid; i < 4096; i += 256)
-        acc += __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(P + i), __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT));
-      if (acc == 1.2345e-30f) lds[L_ST + 40] = acc;   // keeps the loads
-      __syncthreads();
-    }
-  }
-#endif
   const bool is_sel = n == sel;
   float ds[O];
 #pragma unroll
@@ -763,11 +704,7 @@ __device__ __forceinline__ void gnn_tile(const GnnArgs& ga, float* lds, const in
   GSTAMP(5);
   // the hypernet partials are consumed: reuse PART for the dz exchange [block][r][lane]
 #pragma unroll
-#if DDRL_GNN_HW
   for (int r = 0; r < 4; ++r) part[(4 * w + r) * 64 + lane] = dh[r] * (1.f - hw[r] * hw[r]);
-#else
-  for (int r = 0; r < 4; ++r) part[(4 * w + r) * 64 + lane] = dh[r] * (1.f - h[w][r] * h[w][r]);
-#endif
   // layer weight gradients: 16 tiles of 16x16 per matrix over the 16 rows, 4 per wave and
   // matrix; tile slot k of this wave belongs to this workgroup's share (gnn_tile_owner)
   // (slot k of wave w: tile id w + 4 k -> matrix k / 4, row block k % 4, column block w)
@@ -805,13 +742,19 @@ __device__ __forceinline__ void gnn_tile(const GnnArgs& ga, float* lds, const in
 #pragma unroll
   for (int s4 = 0; s4 < 4; ++s4) qb[s4] = c < 4 ? qt[(4 * s4 + q) * 4 + c] : (c == 4 ? 1.f : 0.f);
   GSTAMP(8);
-  // Software-pipelined over the feature rows i of this wave: the dpre tiles of row k + 1 are
-  // computed (MFMA, tanh: VALU) and stored to the other half of a double-buffered LDS tile
-  // while the 16 weight-gradient MFMAs of row k run on operands already in registers.
-  float* tpb = lds + L_TP + 2048 * w;   // [2][4 column blocks][16 x 16]
-  auto dpre_tiles = [&](int k, float* tp) {
+  float* tpb = lds + L_TP + 2048 * w;   // this wave's transpose tiles [4 column blocks][16 x 16]
+  static_assert((GF + 3) / 4 == GNI, "feature rows per wave");
+  // this workgroup's (row k, column block t) pairs (gnn_hbwd_owner)
+#pragma unroll
+  for (int k = 0; k < GNI; ++k) {
+    const int i = w + 4 * k;
+    bool any = false;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) any = any || gnn_hbwd_owner(k, t) == zs;
+    if (!any || i >= GF) continue;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
+      if (gnn_hbwd_owner(k, t) != zs) continue;
       const floatx4 pre = mfma4(we[k][t], qv, be[k][t]);
       floatx4 dp;
 #pragma unroll
@@ -819,72 +762,20 @@ __device__ __forceinline__ void gnn_tile(const GnnArgs& ga, float* lds, const in
         const float wn = tanh_fast(pre[r]);
         dp[r] = fi[k] * dz[t][r] * (1.f - wn * wn);
       }
-      *reinterpret_cast<floatx4*>(tp + 256 * t + tp_w(c, q)) = dp;   // [row c][j 4q + r]
+      *reinterpret_cast<floatx4*>(tpb + 256 * t + tp_w(c, q)) = dp;
     }
-  };
-  constexpr int NK = (GF + 3) / 4;   // feature rows of wave 0 (waves 1..3 have NK or NK - 1)
-  static_assert(NK == GNI, "feature rows per wave");
-  if constexpr (GNN_Z > 1) {
-    // this workgroup's (row k, column block t) pairs (gnn_hbwd_owner), not pipelined
-#pragma unroll
-    for (int k = 0; k < GNI; ++k) {
-      const int i = w + 4 * k;
-      bool any = false;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) any = any || gnn_hbwd_owner(k, t) == zs;
-      if (!any || i >= GF) continue;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if (gnn_hbwd_owner(k, t) != zs) continue;
-        const floatx4 pre = mfma4(we[k][t], qv, be[k][t]);
-        floatx4 dp;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float wn = tanh_fast(pre[r]);
-          dp[r] = fi[k] * dz[t][r] * (1.f - wn * wn);
-        }
-        *reinterpret_cast<floatx4*>(tpb + 256 * t + tp_w(c, q)) = dp;
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if (gnn_hbwd_owner(k, t) != zs) continue;
-        floatx4 acc = splat4(0.f);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) acc = mfma4(tpb[256 * t + tp_r(4 * s4 + q, c)], qb[s4], acc);
-        const int j = i * 64 + 16 * t + 4 * q;
-        if (c < 4) pst4(coh, P + off.wenc + c * GHE + j, acc);
-        else if (c == 4) pst4(coh, P + off.benc + j, acc);
-      }
-    }
-    GSTAMP(9);
-    return;
-  }
-  dpre_tiles(0, tpb);
-#pragma unroll
-  for (int k = 0; k < GNI; ++k) {
-    const int i = w + 4 * k;
-    if (i >= GF) break;
-    const float* tp = tpb + 1024 * (k & 1);
-    float a[4][4];
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) a[s4][t] = tp[256 * t + tp_r(4 * s4 + q, c)];
-    if (k + 1 < GNI && i + 4 < GF) dpre_tiles(k + 1, tpb + 1024 * ((k + 1) & 1));
-    floatx4 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = splat4(0.f);
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[t] = mfma4(a[s4][t], qb[s4], acc[t]);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const int j = i * 64 + 16 * t + 4 * q;                  // acc[r]: column j + r, qd = c
-      if (c < 4) pst4(coh, P + off.wenc + c * GHE + j, acc[t]);
-      else if (c == 4) pst4(coh, P + off.benc + j, acc[t]);
+      if (gnn_hbwd_owner(k, t) != zs) continue;
+      floatx4 acc = splat4(0.f);
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) acc = mfma4(tpb[256 * t + tp_r(4 * s4 + q, c)], qb[s4], acc);
+      const int j = i * 64 + 16 * t + 4 * q;
+      if (c < 4) pst4(coh, P + off.wenc + c * GHE + j, acc);
+      else if (c == 4) pst4(coh, P + off.benc + j, acc);
     }
   }
+  GSTAMP(9);
 }
 
 __device__ __forceinline__ void gnn_tail(const GnnArgs& ga, float* lds, int tile, int net, int zs);   // below
@@ -1086,18 +977,12 @@ __global__ void __launch_bounds__(256) k_gnn_adam(GnnArgs ga, int nred, int n) {
 // other XCD's L2 is never seen, and the wait ends at its bound the same way.  So no stale partial
 // is ever summed, whatever the flag's scope.  The flags are plain (workgroup-scope) stores into
 // the XCD's L2: agent scope (written through, seen across XCDs at once) cost 0.2 us per step at C5
-// (17.76 vs 17.55 us, profiles/r05/gnn_flag_scope_ab.txt); -DDDRL_GNN_FLAG_AGENT=1 builds it.
-#ifndef DDRL_GNN_FLAG_AGENT
-#define DDRL_GNN_FLAG_AGENT 0
-#endif
+// (17.76 vs 17.55 us, profiles/r05/gnn_flag_scope_ab.txt).
 // arrival flag of tile t of combination k: the 32 flags of one combination in one 128-B line,
 // which a reducer's 32 polling lanes read with one request (measured against the flags spread
 // over 8 lines, 4 each: 17.65 / 17.66 vs 17.70 / 17.78 us per step at C5, the same box,
 // profiles/r05/gnn_flag_scope_ab.txt)
-#ifndef DDRL_GNN_FLAG_PACKED
-#define DDRL_GNN_FLAG_PACKED 1
-#endif
-__device__ __forceinline__ int gnn_flag_idx(int k, int t) { return DDRL_GNN_FLAG_PACKED ? 32 * k + t : 8 * t + k; }
+__device__ __forceinline__ int gnn_flag_idx(int k, int t) { return 32 * k + t; }
 __device__ __forceinline__ unsigned gnn_xcc() {
   unsigned x;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
@@ -1152,7 +1037,7 @@ __device__ __forceinline__ void gnn_tail(const GnnArgs& ga, float* lds, int tile
   // the placement record for the host check (capi.cpp gnn_placement_broken)
   if (tid == 0) {
     __hip_atomic_store(ga.flags + gnn_flag_idx(k, tile), (ga.tag << 4) | xcc, __ATOMIC_RELAXED,
-                       DDRL_GNN_FLAG_AGENT ? __HIP_MEMORY_SCOPE_AGENT : __HIP_MEMORY_SCOPE_WORKGROUP);
+                       __HIP_MEMORY_SCOPE_WORKGROUP);
     ga.xcc[32 * k + tile] = (int)xcc;
   }
   const int m = ga.poff[k + 1] - ga.poff[k];
@@ -1236,13 +1121,7 @@ __device__ __forceinline__ void gnn_tail(const GnnArgs& ga, float* lds, int tile
   // every reducer's norm^2 partial (one granule per thread), then the norm in a fixed order
   const int nr_all = ga.rbase[8];
   float gv = 0.f;
-#ifdef DDRL_ABL_GNN_LOCAL_NORM
-  // timing-only cost model (results wrong): the norm from this XCD's own
-  // reducers only -- no granule crosses an XCD
-  const bool ok2 = tid < ga.rbase[k] || tid >= ga.rbase[k + 1] || gnn_wait_gran(ga, ga.gran + tid, t0, gv);
-#else
   const bool ok2 = tid >= nr_all || gnn_wait_gran(ga, ga.gran + tid, t0, gv);
-#endif
   T[64 + tid] = gv;
   if (!__syncthreads_and(ok2)) return;
   RSTAMPB(gi, 2);
@@ -1337,11 +1216,6 @@ static GnnArgs grad_args(const UpdateArgs& u, const UpdateHyper& h, int step, in
                          const GnnScratch& sc, const float* stage, int layer) {
   GnnArgs ga{};
   ga.theta = u.theta; ga.u = u; ga.h = h; ga.step = step; ga.n_graphs = nrows; ga.inv_n = inv_n;
-#ifdef DDRL_ABL_GNN_THETA_RO
-  // timing-only cost model (results wrong): the tiles read their weights
-  // from a buffer no launch writes (the records), as if theta stayed in the reading XCD's L2
-  ga.theta = u.rec;
-#endif
   ga.part = sc.part; ga.part_stride = sc.part_stride; ga.statp = sc.statp; ga.normp = sc.normp;
   ga.bp_cur = sc.bp_cur; ga.grad = u.grad_out ? u.grad_out : sc.grad;
   ga.stage = stage;
@@ -1425,8 +1299,8 @@ void launch_step_gnn(hipStream_t s, const UpdateArgs& u, const UpdateHyper& h, i
   GnnArgs ga = grad_args(u, h, step, nrows, inv_n, sc, stage, layer);
   const int ntiles = ga.ntiles, n = ga.n_params, nred = ga.nred;
   // one launch per step for full 128-row minibatches (32 tiles per combination)
-  if (sc.tail && sc.lists == 0 && ntiles == DDRL_MB / 4 && GNN_Z == 4) gnn_build_owner_lists(s, u, h, inv_n, sc, layer);
-  ga.tail = sc.tail && sc.lists == 1 && ntiles == DDRL_MB / 4 && GNN_Z == 4;
+  if (sc.tail && sc.lists == 0 && ntiles == DDRL_MB / 4) gnn_build_owner_lists(s, u, h, inv_n, sc, layer);
+  ga.tail = sc.tail && sc.lists == 1 && ntiles == DDRL_MB / 4;
   if (ga.tail) {
     sc.seq = (sc.seq + 1) & 0x0FFFFFFFu;   // 28-bit tags (the flags hold tag << 4 | XCC id)
     if (sc.seq == 0) sc.seq = 1;           // tags never 0 (the buffers start zeroed)

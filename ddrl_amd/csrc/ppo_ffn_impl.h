@@ -38,34 +38,11 @@
 #else
 #define DDRL_XCHG_IS_ATOMIC 0
 #endif
-// Adam's small-parameter slots past nsb aimed at a sink word instead of masked (A/B: -DDDRL_SINK=0)
-#ifndef DDRL_SINK
-#define DDRL_SINK 1
-#endif
-// Per-lane predicates "feature < d" out of the step loop (the inputs of features >= d zeroed
-// instead; -DDDRL_PADZERO=0: the predicates, for A/B)
-#ifndef DDRL_PADZERO
-#define DDRL_PADZERO 1
-#endif
-// LSB-tagged quads for fused launches (round 4; -DDDRL_LX=0: the {value, tag} pairs everywhere)
-#ifndef DDRL_LX
-#define DDRL_LX 1
-#endif
 // the peer TU: atomic granules for the norm exchange and the gradient launches' pairs, quads at
 // system scope for the fused launches' partner exchange
 #define DDRL_XCHG_LXSYS (DDRL_FFN_AT == 2)
-// where the row split issues the next step's record gathers: 0 = behind the partner exchange's
-// first poll (vmcnt retires in order), 1 = right after sync #1 (round 6 A/B)
-#ifndef DDRL_GATHER_EARLY
-#define DDRL_GATHER_EARLY 0
-#endif
-// DDRL_ABL_PEER4: the timing-only cost model of a four-rank peer mode, in the
-// peer TU only: the weight-gradient K of a 32-row share and two more partners' quad reads at
-// system scope (the four-way split model of DESIGN.md section 6.2 on the peer protocol)
-#if defined(DDRL_ABL_PEER4) && DDRL_FFN_AT == 2
-#define DDRL_ABL_HALF_DW
-#define DDRL_ABL_XCHG3
-#endif
+// Fused launches exchange LSB-tagged quads (round 4), except under the atomic protocol, which
+// keeps the {value, tag} pairs everywhere
 #define DDRL_LX_ON (!DDRL_XCHG_IS_ATOMIC || DDRL_XCHG_LXSYS)
 
 namespace {
@@ -447,20 +424,7 @@ namespace {
 // L1.  Measured one-hop latency (tools/xchg_bench.hip, MI355X): plain store / sc1 load
 // 0.24 us, sc1 store / sc1 load 0.50 us (the sc1 store writes through to memory), sc0 loads
 // never see the partner (they hit the stale L1 line).
-#ifndef DDRL_GX_ST
-#define DDRL_GX_ST 0
-#endif
-#ifndef DDRL_GX_LD
-#define DDRL_GX_LD 16
-#endif
-#ifndef DDRL_GX_INV
-#define DDRL_GX_INV 0
-#endif
-__device__ __forceinline__ void xchg_inv_l1() {
-#if DDRL_GX_INV
-  asm volatile("buffer_inv sc0" ::: "memory");
-#endif
-}
+constexpr int kGxSt = 0, kGxLd = 16;   // plain store, sc1 load
 // Once any exchange has waited this long (100 MHz ticks), the waiter also polls the error
 // word, so one timed-out exchange ends every later wait at once instead of each one
 // spinning to its own timeout.
@@ -542,7 +506,7 @@ __device__ __forceinline__ gx_box_t gx_rsrc(unsigned long long* box) {
 __device__ __forceinline__ void gx_put(gx_box_t r, int j, float v0, float v1, unsigned tag, bool coh) {
   const v4u g = {__float_as_uint(v0), tag, __float_as_uint(v1), tag};
   if (coh) __builtin_amdgcn_raw_buffer_store_b128(g, r, (j * 256 + (int)threadIdx.x) * 16, 0, 16);
-  else __builtin_amdgcn_raw_buffer_store_b128(g, r, (j * 256 + (int)threadIdx.x) * 16, 0, DDRL_GX_ST);
+  else __builtin_amdgcn_raw_buffer_store_b128(g, r, (j * 256 + (int)threadIdx.x) * 16, 0, kGxSt);
 }
 // Norm granule (8 bytes: tag << 32 | value), one 64-bit access each way, same policy.
 __device__ __forceinline__ void xchg_store(unsigned long long* g, unsigned long long v, bool coh) {
@@ -550,13 +514,12 @@ __device__ __forceinline__ void xchg_store(unsigned long long* g, unsigned long 
   typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
   const v2u_t x = {(unsigned)v, (unsigned)(v >> 32)};
   if (coh) __builtin_amdgcn_raw_buffer_store_b64(x, r, 0, 0, 16);
-  else __builtin_amdgcn_raw_buffer_store_b64(x, r, 0, 0, DDRL_GX_ST);
+  else __builtin_amdgcn_raw_buffer_store_b64(x, r, 0, 0, kGxSt);
 }
 __device__ __forceinline__ unsigned long long xchg_load(unsigned long long* g) {
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(g, 0, 8, 0x00020000);
   typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
-  xchg_inv_l1();
-  const v2u_t x = __builtin_amdgcn_raw_buffer_load_b64(r, 0, 0, DDRL_GX_LD);
+  const v2u_t x = __builtin_amdgcn_raw_buffer_load_b64(r, 0, 0, kGxLd);
   return ((unsigned long long)x[1] << 32) | x[0];
 }
 // The partner's NP pairs of this lane: all loads in flight, re-polled until every tag
@@ -568,9 +531,8 @@ __device__ __forceinline__ bool gx_get(gx_box_t r, unsigned tag, float* out, int
   const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
   bool first = true;
   for (;;) {
-    xchg_inv_l1();
 #pragma unroll
-    for (int j = 0; j < NP; ++j) g[j] = __builtin_amdgcn_raw_buffer_load_b128(r, (j * 256 + (int)threadIdx.x) * 16, 0, DDRL_GX_LD);
+    for (int j = 0; j < NP; ++j) g[j] = __builtin_amdgcn_raw_buffer_load_b128(r, (j * 256 + (int)threadIdx.x) * 16, 0, kGxLd);
     if (first) { after_first(); first = false; }
     bool ok = true;
 #pragma unroll
@@ -614,34 +576,27 @@ typedef __amdgpu_buffer_rsrc_t lx_box_t;
 __device__ __forceinline__ lx_box_t lx_rsrc(unsigned long long* box) {
   return __builtin_amdgcn_make_buffer_rsrc(box, 0, GX_MAX_PAIRS * 256 * 16, 0x00020000);
 }
-#define DDRL_LX_ST 17
-#define DDRL_LX_LD 17
+constexpr int kLxSt = 17, kLxLd = 17;   // sc0 sc1
 #else
 typedef gx_box_t lx_box_t;
 __device__ __forceinline__ lx_box_t lx_rsrc(unsigned long long* box) { return gx_rsrc(box); }
-#define DDRL_LX_ST DDRL_GX_ST
-#define DDRL_LX_LD DDRL_GX_LD
+constexpr int kLxSt = kGxSt, kLxLd = kGxLd;
 #endif
 __device__ __forceinline__ void gx_put4(lx_box_t r, int j, float a, float b, float c, float d, unsigned bit) {
   const v4u g = {__float_as_uint(lx_t(a, bit)), __float_as_uint(lx_t(b, bit)), __float_as_uint(lx_t(c, bit)),
                  __float_as_uint(lx_t(d, bit))};
-  __builtin_amdgcn_raw_buffer_store_b128(g, r, (j * 256 + (int)threadIdx.x) * 16, 0, DDRL_LX_ST);
+  __builtin_amdgcn_raw_buffer_store_b128(g, r, (j * 256 + (int)threadIdx.x) * 16, 0, kLxSt);
 }
-// NX > 0: the timing-only cost-model build of a four-way split; NX more quads (another outbox,
-// rx) loaded with every poll and returned unchecked
-template <int NQ, int NX = 0, typename F>
-__device__ __forceinline__ bool gx_get4(lx_box_t r, unsigned bit, float* out, int* err, F&& after_first,
-                                        lx_box_t rx = lx_box_t()) {
+// The partner's NQ quads of this lane, polled as gx_get polls the pairs.
+template <int NQ, typename F>
+__device__ __forceinline__ bool gx_get4(lx_box_t r, unsigned bit, float* out, int* err, F&& after_first) {
   bool lost = false;
-  v4u g[NQ + NX];
+  v4u g[NQ];
   const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
   bool first = true;
   for (;;) {
-    xchg_inv_l1();
 #pragma unroll
-    for (int j = 0; j < NQ; ++j) g[j] = __builtin_amdgcn_raw_buffer_load_b128(r, (j * 256 + (int)threadIdx.x) * 16, 0, DDRL_LX_LD);
-#pragma unroll
-    for (int j = 0; j < NX; ++j) g[NQ + j] = __builtin_amdgcn_raw_buffer_load_b128(rx, (j * 256 + (int)threadIdx.x) * 16, 0, DDRL_LX_LD);
+    for (int j = 0; j < NQ; ++j) g[j] = __builtin_amdgcn_raw_buffer_load_b128(r, (j * 256 + (int)threadIdx.x) * 16, 0, kLxLd);
     if (first) { after_first(); first = false; }
     unsigned bad = 0;
 #pragma unroll
@@ -649,14 +604,14 @@ __device__ __forceinline__ bool gx_get4(lx_box_t r, unsigned bit, float* out, in
     if ((bad & 1u) == 0) break;
     if (xchg_abandon(t0, err)) {
 #pragma unroll
-      for (int j = 0; j < NQ + NX; ++j) g[j] = v4u{0u, 0u, 0u, 0u};
+      for (int j = 0; j < NQ; ++j) g[j] = v4u{0u, 0u, 0u, 0u};
       lost = true;
       break;
     }
     __builtin_amdgcn_s_sleep(1);
   }
 #pragma unroll
-  for (int j = 0; j < NQ + NX; ++j)
+  for (int j = 0; j < NQ; ++j)
 #pragma unroll
     for (int k = 0; k < 4; ++k) out[4 * j + k] = __uint_as_float(g[j][k]);
   return lost;
@@ -731,20 +686,6 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
   constexpr int ROWS = DDRL_MB / KSP;
   constexpr int NT = Geo<NW, ROWS>::NT, RT = Geo<NW, ROWS>::RT, NS1 = Geo<NW, ROWS>::NS1, NS2 = Geo<NW, ROWS>::NS2;
   constexpr bool PAD = update_pad(A, KSP);   // layout of the weight images (common.h)
-#ifdef DDRL_ABL_NO_MOMENTS
-  constexpr bool NOMOM = KSP == 2;
-#else
-  constexpr bool NOMOM = false;
-#endif
-  // DDRL_ABL_ADAM_SPLIT: timing-only cost model (round 6) of Adam split over the two row halves
-  // -- each half updates half of the parameters, then reads its partner's half of the updated
-  // weights (results wrong)
-#ifdef DDRL_ABL_ADAM_SPLIT
-  constexpr bool ADAM_SPLIT = KSP == 2;
-#else
-  constexpr bool ADAM_SPLIT = false;
-#endif
-  const size_t gx_box_n = (size_t)GX_MAX_PAIRS * 256 * 2;   // granules per outbox
   const int wkq = ub.own_kq < 0 ? 0 : ub.own_kq;   // the half that writes back and writes the statistics
   const UpdateHyper& H = ub.h;
   const int d = U.d;
@@ -772,13 +713,6 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
 
   NetLds W;
   constexpr int LD = ROWS + 8;              // feature-major image stride
-  // K (rows) of the weight-gradient tiles; the timing-only cost-model build
-  // -DDDRL_ABL_HALF_DW halves it (the weight-gradient work of a four-way row split)
-#ifdef DDRL_ABL_HALF_DW
-  constexpr int DWR = ROWS / 2;
-#else
-  constexpr int DWR = ROWS;
-#endif
   float* bufA = lds + branch_lds_floats(PAD);    // feature-major [64][LD]: H1, then X
   float* bufB = bufA + 64 * LD;             // feature-major [64][LD]: dZ2, then dZ1
   float* Pb = bufB + 64 * LD;               // [NW][NSB] per-wave partial small grads
@@ -860,7 +794,7 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     // [0, 64) per-wave statistics, [64, 72) norm partials, 80 / 81, [96, 104) the combined
     // statistics, and idxb from 128 on), so Adam's small-parameter LDS accesses need no lane
     // predicate in the step loop
-    sp_lds[k] = DDRL_SINK ? (int)(red + 127 - lds) : 0;
+    sp_lds[k] = (int)(red + 127 - lds);
     if (e < nsb) {
       int pidx; float* lp;
       small_param<OB>(e, bo, W, pidx, lp);
@@ -1041,11 +975,6 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     }
     STAMP(4);
     __syncthreads();                                     // #1: H1, dZ2, partials visible
-#if DDRL_GATHER_EARLY
-    // the row split's prefetch of step + 1's records, issued here: every lane read its rows of
-    // this step at the top (load_row), and the gathers now have the rest of the step to land
-    if (KSP == 2 && step + 1 < last) issue_rows<NW, ROWS>(U.rec, stride, cpr, cpr_l, inv_cpr_l, idxb, stg, U.R, ub.lds_bytes);
-#endif
     STAMP(5);
     const unsigned gtag = xchg_tag(ub.epoch, step);
     const int gstep = step + (int)ub.lx_base;            // outbox parity and quad tag bit
@@ -1094,12 +1023,12 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     if constexpr (HMF) {
       static_assert(NW == 4, "one head tile (16 features) per wave");
       floatx4 gh;
-      dw_tiles_fm_head<DWR, NS1, ROWS + 8>(bufA, bufB, tfa, w & 3, gt, bufH, bufD, w, gh);   // dW2 tiles + dWo
+      dw_tiles_fm_head<ROWS, NS1, ROWS + 8>(bufA, bufB, tfa, w & 3, gt, bufH, bufD, w, gh);   // dW2 tiles + dWo
       if (c < OB)
 #pragma unroll
         for (int r = 0; r < 4; ++r) Pb[(16 * w + 4 * q + r) * OB + c] = gh[r];
     } else {
-      dw_tiles_fm<DWR, NS1, ROWS + 8>(bufA, bufB, tfa, w & 3, gt);   // dW2 tiles of this wave
+      dw_tiles_fm<ROWS, NS1, ROWS + 8>(bufA, bufB, tfa, w & 3, gt);   // dW2 tiles of this wave
     }
 #else
     for (int i = 0; i < NS1; ++i) gt[i] = splat4(0.f);
@@ -1156,11 +1085,11 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
 #ifdef DDRL_ABL_NO_DW1
       n1 = -1;
 #endif
-      if (n1 == NS2) dw_tiles_fm<DWR, NS2, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+      if (n1 == NS2) dw_tiles_fm<ROWS, NS2, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
       else if constexpr (NS2 >= 3) {
-        if (n1 == 2) dw_tiles_fm<DWR, 2, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
-        else if (n1 == 1) dw_tiles_fm<DWR, 1, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
-      } else if (n1 == 1) dw_tiles_fm<DWR, 1, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+        if (n1 == 2) dw_tiles_fm<ROWS, 2, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+        else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+      } else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
     }
     STAMP(10);
     if constexpr (KSP == 2) {
@@ -1180,30 +1109,10 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
       }
 #if DDRL_LX_ON
       if constexpr (LX) {
-#ifdef DDRL_ABL_XCHG3P
-        // timing-only cost-model build: three partners' outboxes polled at once, every load of
-        // the three in flight together, and their sum (here the partner's outbox, checked, and
-        // 2 NQ quads of its other-parity outbox, unchecked)
-        float o4[12 * NQ];
-        gx_get4<NQ, 2 * NQ>(lx_rsrc(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + (gstep & 1)) * gx_box), lbit, o4, ub.err, [&] {
-          if (!DDRL_GATHER_EARLY && step + 1 < last) issue_rows<NW, ROWS>(U.rec, stride, cpr, cpr_l, inv_cpr_l, idxb, stg, U.R, ub.lds_bytes);
-        }, lx_rsrc(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + ((gstep + 1) & 1)) * gx_box));
-#pragma unroll
-        for (int k = 0; k < 4 * NQ; ++k) o4[k] = (o4[k] + o4[4 * NQ + k]) + o4[8 * NQ + k];
-#else
         float o4[4 * NQ];
         gx_get4<NQ>(lx_rsrc(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + (gstep & 1)) * gx_box), lbit, o4, ub.err, [&] {
-          if (!DDRL_GATHER_EARLY && step + 1 < last) issue_rows<NW, ROWS>(U.rec, stride, cpr, cpr_l, inv_cpr_l, idxb, stg, U.R, ub.lds_bytes);
+          if (step + 1 < last) issue_rows<NW, ROWS>(U.rec, stride, cpr, cpr_l, inv_cpr_l, idxb, stg, U.R, ub.lds_bytes);
         });
-#endif
-#if defined(DDRL_ABL_XCHG3)
-        for (int extra = 0; extra < 2; ++extra) {   // the cost-model build, as below
-          float o2[4 * NQ];
-          gx_get4<NQ>(lx_rsrc(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + (gstep & 1)) * gx_box), lbit, o2, ub.err, [] {});
-#pragma unroll
-          for (int k = 0; k < 4 * NQ; ++k) o4[k] += 0.f * o2[k];
-        }
-#endif
         // both workgroups add the same two LSB-replaced partials
 #pragma unroll
         for (int k = 0; k < NSLOT; ++k) gs[k] = lx_t(gs[k], lbit) + o4[k];
@@ -1221,20 +1130,10 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
       // retire first: vmcnt is in order; a re-poll then waits for them too): 13.0 -> 12.9 us
       // per step against issuing them after the exchange
       gx_get<NP>(gx_rsrc(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + (gstep & 1)) * gx_box), gtag, o, ub.err, [&] {
-        if (!DDRL_GATHER_EARLY && step + 1 < last) issue_rows<NW, ROWS>(U.rec, stride, cpr, cpr_l, inv_cpr_l, idxb, stg, U.R, ub.lds_bytes);
+        if (step + 1 < last) issue_rows<NW, ROWS>(U.rec, stride, cpr, cpr_l, inv_cpr_l, idxb, stg, U.R, ub.lds_bytes);
       });
 #else
       gx_get<NP>(gx_rsrc(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + (gstep & 1)) * gx_box), gtag, o, ub.err, [] {});
-#endif
-#ifdef DDRL_ABL_XCHG3
-      // timing-only cost-model build: the two more partner reads of a four-way row split, one
-      // after the other (each a poll of the partner's outbox and the transfer of its partials)
-      for (int extra = 0; extra < 2; ++extra) {
-        float o2[2 * NP];
-        gx_get<NP>(gx_rsrc(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + (gstep & 1)) * gx_box), gtag, o2, ub.err, [] {});
-#pragma unroll
-        for (int k = 0; k < 2 * NP; ++k) o[k] += 0.f * o2[k];
-      }
 #endif
       if constexpr (LSBX) {   // the atomic protocol of a fused launch: the quads' sums
 #pragma unroll
@@ -1272,11 +1171,10 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     for (int i = 0; i < NTS; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int f = 16 * tfa[i] + 4 * q + r;
         // the weights of features >= d: zero gradient (their inputs are zeroed in load_row), so
         // only the uniform tile predicate remains in the loop (the generic KS1 = 12 instance
         // zeroes every feature >= d there too)
-        if (tv[i] && (i < NS1 || DDRL_PADZERO || f < d)) ss += gt[i][r] * gt[i][r];
+        if (tv[i]) ss += gt[i][r] * gt[i][r];
       }
 
     if (U.grad_out) {   // data-parallel mode: export the raw gradient of this branch
@@ -1359,23 +1257,16 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
         for (int r = 0; r < 4; ++r)
           th[i][r] = (i < NS1 ? W.w2 : W.w1)[ebase[r] + lds_blk(PAD) * tfa[i]];
 #pragma unroll
-      for (int k = 0; k < NSLOT; ++k) {
-        const int e = tid + NT * k;
-        ts[k] = 0.f;
-        ts[k] = (DDRL_SINK || e < nsb) ? lds[sp_lds[k]] : 0.f;
-      }
+      for (int k = 0; k < NSLOT; ++k) ts[k] = lds[sp_lds[k]];   // (slots past nsb: the sink word)
       // two elements per instruction (v_pk_* ops): the same fused operations, element by
       // element, as the scalar form g = gt s; m += (gt s - m) c1; v += (g g - v) c2;
       // theta -= (m alpha) / (sqrt(v) + eps)
 #pragma unroll
-      for (int i = 0; i < (ADAM_SPLIT ? (NTS + 1) / 2 : NTS); ++i)
+      for (int i = 0; i < NTS; ++i)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const float2v gr = {gt[i][2 * h], gt[i][2 * h + 1]};
-          // NOMOM: the timing-only cost model of VERDICT r05 item 3 -- the weight tiles' moments
-          // not carried across steps, i.e. their 2 x 4 x NTS VGPRs out of the step loop (wrong results)
-          float2v m2 = {NOMOM ? 0.f : mt[i][2 * h], NOMOM ? 0.f : mt[i][2 * h + 1]},
-                  v2 = {NOMOM ? 0.f : vt4[i][2 * h], NOMOM ? 0.f : vt4[i][2 * h + 1]};
+          float2v m2 = {mt[i][2 * h], mt[i][2 * h + 1]}, v2 = {vt4[i][2 * h], vt4[i][2 * h + 1]};
           const float2v sc = {scale, scale}, k1 = {c1, c1}, k2 = {c2, c2}, al = {alpha, alpha};
           const float2v g = gr * sc;
           m2 = __builtin_elementwise_fma(__builtin_elementwise_fma(gr, sc, -m2), k1, m2);
@@ -1384,15 +1275,13 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
           den = den + (float2v){H.eps, H.eps};
           const float2v rc = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
           const float2v t2 = __builtin_elementwise_fma(-(m2 * al), rc, (float2v){th[i][2 * h], th[i][2 * h + 1]});
-          if constexpr (!NOMOM) {
-            mt[i][2 * h] = m2[0]; mt[i][2 * h + 1] = m2[1];
-            vt4[i][2 * h] = v2[0]; vt4[i][2 * h + 1] = v2[1];
-          }
+          mt[i][2 * h] = m2[0]; mt[i][2 * h + 1] = m2[1];
+          vt4[i][2 * h] = v2[0]; vt4[i][2 * h + 1] = v2[1];
           th[i][2 * h] = t2[0]; th[i][2 * h + 1] = t2[1];
         }
 
 #pragma unroll
-      for (int k = 0; k < (ADAM_SPLIT ? (NSLOT + 1) / 2 : NSLOT); ++k) {
+      for (int k = 0; k < NSLOT; ++k) {
         const float g = gs[k] * scale;
         ms[k] = ms[k] + (g - ms[k]) * c1;
         vs[k] = vs[k] + (g * g - vs[k]) * c2;
@@ -1402,31 +1291,12 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
       for (int i = 0; i < NTS; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int f = 16 * tfa[i] + 4 * q + r;
           // (rows >= d of the W1 image: their gradient and moments are zero up to the exchange's
           // tag bits, they meet only zeroed inputs, and the write-back to HBM skips them)
-          if (tv[i] && (i < NS1 || DDRL_PADZERO || f < d))
-            (i < NS1 ? W.w2 : W.w1)[ebase[r] + lds_blk(PAD) * tfa[i]] = th[i][r];
+          if (tv[i]) (i < NS1 ? W.w2 : W.w1)[ebase[r] + lds_blk(PAD) * tfa[i]] = th[i][r];
         }
 #pragma unroll
-      for (int k = 0; k < NSLOT; ++k) {
-        const int e = tid + NT * k;
-        if (DDRL_SINK || e < nsb) lds[sp_lds[k]] = ts[k];
-      }
-    }
-#endif
-#if DDRL_LX_ON
-    if constexpr (ADAM_SPLIT && LX) {
-      // the cost model's second hop: the partner's half of the updated weights (half the quads
-      // of its outbox, already valid for this step), read before sync #6
-      const int gstep = step + (int)ub.lx_base;
-      float o2[4 * ((NQ + 1) / 2)];
-      gx_get4<(NQ + 1) / 2>(lx_rsrc(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + (gstep & 1)) * gx_box_n), lx_bit(gstep), o2,
-                             ub.err, [] {});
-      float acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4 * ((NQ + 1) / 2); ++k) acc += o2[k];
-      if (acc == 1.2345e-30f) red[127] = acc;   // keeps the loads
+      for (int k = 0; k < NSLOT; ++k) lds[sp_lds[k]] = ts[k];
     }
 #endif
     b1p = b1p * H.b1;
@@ -1454,10 +1324,8 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
       const int f = 16 * tfa[i] + 4 * q + r, o = 16 * tfo[i] + c;
       if (!(tv[i] && (i < NS1 || f < d))) continue;
       const int pidx = (i < NS1 ? bo.w2 : bo.w1) + f * 64 + o;
-      if constexpr (!NOMOM) {
-        U.m[pidx] = mt[i][r];
-        U.v[pidx] = vt4[i][r];
-      }
+      U.m[pidx] = mt[i][r];
+      U.v[pidx] = vt4[i][r];
     }
 #pragma unroll
   for (int k = 0; k < NSLOT; ++k) {
@@ -1534,7 +1402,7 @@ void DDRL_FFN_LAUNCH(hipStream_t s, const UpdateArgs* ua, const UpdateHyper& h, 
 #if DDRL_FFN_KSP == 2
   // only the fused row-split kernels (LSB quads) live here; the KSP = 1 kernels and the
   // gradient-export launches are built in ppo_ffn_k1.hip
-  if (!(ksp == 2 && ua[0].grad_out == nullptr && DDRL_LX)) {
+  if (!(ksp == 2 && ua[0].grad_out == nullptr)) {
     launch_update_ffn_k1(s, ua, h, nrows, inv_n, A, d, stride, cup, xchg, gx, ksp, err, epoch_ctr, xcc, own_kq, lx_base);
     return;
   }
@@ -1557,7 +1425,7 @@ void DDRL_FFN_LAUNCH(hipStream_t s, const UpdateArgs* ua, const UpdateHyper& h, 
   ub.epoch = (*epoch_ctr)++ % 4095u + 1u;
   // fused launches (no gradient export) exchange LSB-tagged quads: their outboxes start cleared
   // in every launch (one fill per iteration); gradient launches keep the epoch-tagged pairs
-  const bool lx = ksp == 2 && ua[0].grad_out == nullptr && DDRL_LX;
+  const bool lx = ksp == 2 && ua[0].grad_out == nullptr;
   if (ub.epoch == 1) (void)hipMemsetAsync(xchg, 0, sizeof(unsigned long long) * 8 * DDRL_MAXP, s);
   // (peer mode: gx is shared with the peer context's launch, which may be running; it is cleared
   // when the peers attach, ddrl_peer_attach, and the quads' tag bits follow the pair's global

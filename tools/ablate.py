@@ -5,7 +5,7 @@ one phase (results are wrong; only the per-step time matters) and reports us/ste
     python tools/ablate.py run [envs] [variants...]   # on the GPU box
 
 A variant is a comma-separated list of macro definitions (`DDRL_ABL_NO_DW2`,
-`DDRL_GX_ST=16,DDRL_GX_LD=16`); "" is the baseline build.
+`DDRL_ABL_NO_DW2,DDRL_ABL_NO_DW1`); "" is the baseline build.
 """
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
