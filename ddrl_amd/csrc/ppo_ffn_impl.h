@@ -255,15 +255,26 @@ struct RowData {
 // reads then start in 16 different banks); the pad chunk repeats the row's last chunk.
 // Issued by waves 0 .. NW-2: the last wave keeps its vector-memory counter free for the
 // norm exchange (an early partner poll would otherwise wait for the gathers too).
+// Two halves: rows_prepare reads the staged row indices and forms every lane's source address,
+// rows_fire issues the gathers.  The row split runs the first half under the latency of its
+// partner poll (gx_get4c) and the second after sync #4, so no poll ever queues behind a
+// gather; issue_rows is both, back to back.
 template <int NW, int ROWS>
-__device__ __forceinline__ void issue_rows(const float* rec, int stride, int cpr, int cpr_l, float inv_cpr_l,
-                                           const int* idxb, float* stg, int R, unsigned lds_bytes) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
-  if (w == NW - 1) return;
+struct RowGather {
   // at most 20 chunks per record (fcnet records: d <= 48, A <= 8 -> stride <= 80 floats), so a
   // wave issues at most MI batches; every staged row index is read from LDS first (one
   // latency for all batches), then the gathers go out back to back
-  constexpr int MI = (ROWS * 20 + 64 * (NW - 1) - 1) / (64 * (NW - 1));
+  static constexpr int MI = (ROWS * 20 + 64 * (NW - 1) - 1) / (64 * (NW - 1));
+  const float* src[MI];
+};
+template <int NW, int ROWS>
+__device__ __forceinline__ void rows_prepare(RowGather<NW, ROWS>& G, const float* rec, int stride, int cpr, int cpr_l,
+                                             float inv_cpr_l, const int* idxb, int R) {
+  constexpr int MI = RowGather<NW, ROWS>::MI;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
+#pragma unroll
+  for (int it = 0; it < MI; ++it) G.src[it] = rec;
+  if (w == NW - 1) return;
   const int nchunk = ROWS * cpr_l;
   int idx[MI], kk[MI];
 #pragma unroll
@@ -279,17 +290,36 @@ __device__ __forceinline__ void issue_rows(const float* rec, int stride, int cpr
   }
 #pragma unroll
   for (int it = 0; it < MI; ++it) {
+    int i = idx[it];
+    if (64 * w + 64 * (NW - 1) * it + lane < nchunk && !BCHK(i >= 0 && i < R, 1)) i = 0;
+    G.src[it] = rec + (size_t)i * stride + 4 * kk[it];
+  }
+  (void)R;
+}
+template <int NW, int ROWS>
+__device__ __forceinline__ void rows_fire(const RowGather<NW, ROWS>& G, int cpr_l, float* stg, unsigned lds_bytes) {
+  constexpr int MI = RowGather<NW, ROWS>::MI;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
+  if (w == NW - 1) return;
+  const int nchunk = ROWS * cpr_l;
+  const unsigned stg_a = lds_addr(stg);   // one generic -> LDS cast for all batches
+#pragma unroll
+  for (int it = 0; it < MI; ++it) {
     const int base = 64 * w + 64 * (NW - 1) * it;          // wave-uniform
     if (base >= nchunk) break;
-    const unsigned dst = __builtin_amdgcn_readfirstlane(lds_addr(stg + 4 * base));
+    const unsigned dst = __builtin_amdgcn_readfirstlane(stg_a + 16u * (unsigned)base);
     if (base + lane < nchunk) {
-      int i = idx[it];
-      if (!BCHK(i >= 0 && i < R, 1)) i = 0;
-      if (BCHK(dst + 16u * (unsigned)lane + 16u <= lds_bytes, 3))
-        glds16(rec + (size_t)i * stride + 4 * kk[it], dst);
+      if (BCHK(dst + 16u * (unsigned)lane + 16u <= lds_bytes, 3)) glds16(G.src[it], dst);
     }
   }
-  (void)R; (void)lds_bytes;
+  (void)lds_bytes;
+}
+template <int NW, int ROWS>
+__device__ __forceinline__ void issue_rows(const float* rec, int stride, int cpr, int cpr_l, float inv_cpr_l,
+                                           const int* idxb, float* stg, int R, unsigned lds_bytes) {
+  RowGather<NW, ROWS> G;
+  rows_prepare<NW, ROWS>(G, rec, stride, cpr, cpr_l, inv_cpr_l, idxb, R);
+  rows_fire<NW, ROWS>(G, cpr_l, stg, lds_bytes);
 }
 
 // staging-row chunks for a record of `stride` floats (the A = 8 kernels keep the plain
@@ -393,16 +423,21 @@ __device__ __forceinline__ int perm_slot(const UpdateArgs& U, int step) {
 // workgroup, accumulated over the steps of one launch; no stamp executes in the real build.
 #ifdef DDRL_STAMPS
 __device__ unsigned long long g_stamps[32][16];
+__device__ unsigned g_poll_stale[32][8];   // first partner polls that missed, per workgroup and wave
 #define STAMP_INIT unsigned long long st_prev = __builtin_amdgcn_s_memtime(), st_acc[16] = {0};
 #ifndef DDRL_STAMP_TID   // the stamped thread (lane 0 of a wave): per-wave diagnostic builds
 #define DDRL_STAMP_TID 0
 #endif
 #define STAMP(k) do { if (tid == DDRL_STAMP_TID) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_prev; st_prev = t_; } } while (0)
-#define STAMP_DONE do { if (tid == DDRL_STAMP_TID) for (int k_ = 0; k_ < 16; ++k_) g_stamps[blockIdx.x][k_] = st_acc[k_]; } while (0)
+#define STAMP_DONE do { if (tid == DDRL_STAMP_TID) for (int k_ = 0; k_ < 16; ++k_) g_stamps[blockIdx.x][k_] = st_acc[k_]; \
+                        if (lane == 0) g_poll_stale[blockIdx.x][w & 7] = st_stale; } while (0)
 }  // namespace
 #if !DDRL_FFN_AT && DDRL_FFN_KSP != 1
 extern "C" int ddrl_diag_stamps(unsigned long long* host) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(g_stamps)) == hipSuccess ? 0 : -1;
+}
+extern "C" int ddrl_diag_poll_stale(unsigned* host) {
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_poll_stale), sizeof(g_poll_stale)) == hipSuccess ? 0 : -1;
 }
 #endif
 namespace {
@@ -616,6 +651,65 @@ __device__ __forceinline__ bool gx_get4(lx_box_t r, unsigned bit, float* out, in
     for (int k = 0; k < 4; ++k) out[4 * j + k] = __uint_as_float(g[j][k]);
   return lost;
 }
+#if !DDRL_XCHG_LXSYS
+#define DDRL_LX_ASMPOLL 1
+// gx_get4 of the default protocol with its loads and its wait written out.  after_first runs
+// under the first poll's latency: the row split forms the addresses of the next step's record
+// gathers there (rows_prepare) and issues the gathers after sync #4 (rows_fire), so neither a
+// poll nor a re-poll ever queues behind an HBM read -- loads retire in order, and the compiler,
+// which cannot see the LDS-DMA gathers (glds16), guards polled registers with vmcnt(0).  The
+// loads are asm so that the hook sits between them and their wait (the sched_barriers pin it);
+// the empty asms after the wait take the quads as in/out operands: volatile asm statements
+// keep their order, so no use of a quad can move above the wait.  Nothing but this workgroup's
+// own puts is outstanding at the poll, so the wait is vmcnt(0).  `stale` (diagnostic build):
+// counts the first polls of this wave that missed.
+template <int NQ, typename F>
+__device__ __forceinline__ bool gx_get4c(unsigned long long* box, unsigned bit, float* out, int* err, unsigned& stale,
+                                         F&& after_first) {
+  bool lost = false;
+  v4u g[NQ];
+  const unsigned long long ba = (unsigned long long)box;
+  // the resource words of gx_rsrc, in SGPRs
+  const v4u rs = {(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ba),
+                  (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(ba >> 32) & 0xffffu)),
+                  (unsigned)(GX_MAX_PAIRS * 256 * 16), 0x00020000u};
+  const unsigned voff = (unsigned)threadIdx.x * 16u;
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  bool first = true;
+  for (;;) {
+#pragma unroll
+    for (int j = 0; j < NQ; ++j)
+      asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen sc1" : "=v"(g[j]) : "v"(voff), "s"(rs), "s"(j * 4096));
+    __builtin_amdgcn_sched_barrier(0);
+    if (first) after_first();
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) asm volatile("" : "+v"(g[j]));
+    unsigned bad = 0;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) bad |= (g[j][0] ^ bit) | (g[j][1] ^ bit) | (g[j][2] ^ bit) | (g[j][3] ^ bit);
+#ifdef DDRL_STAMPS
+    if (first && __builtin_amdgcn_ballot_w64((bad & 1u) != 0)) ++stale;
+#endif
+    first = false;
+    if ((bad & 1u) == 0) break;
+    if (xchg_abandon(t0, err)) {
+#pragma unroll
+      for (int j = 0; j < NQ; ++j) g[j] = v4u{0u, 0u, 0u, 0u};
+      lost = true;
+      break;
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+  (void)stale;
+#pragma unroll
+  for (int j = 0; j < NQ; ++j)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[4 * j + k] = __uint_as_float(g[j][k]);
+  return lost;
+}
+#endif
 #endif
 
 // dH2^T = Wo . dout^T on the matrix cores (policy head, O = 2A >= 4 outputs): one
@@ -829,6 +923,8 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
   __syncthreads();
 
   const float inv_rows = 1.f / (float)ub.nrows;
+  unsigned st_stale = 0;   // diagnostic build: first partner polls of this wave that missed
+  (void)st_stale;
   STAMP_INIT
   for (int step = U.step0; step < last; ++step) {
     // Adam's step size (tf1: lr sqrt(1 - b2^t) / (1 - b1^t), correctly rounded sqrt and
@@ -1019,6 +1115,8 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     };
     if constexpr (KSP == 2 && !HMF) put_small();
     floatx4 gt[NTS];
+    RowGather<NW, ROWS> G;   // row split: the next step's gathers, prepared under the partner poll
+    (void)G;
 #ifndef DDRL_ABL_NO_DW2   // ablation builds (timing only): skip a phase
     if constexpr (HMF) {
       static_assert(NW == 4, "one head tile (16 features) per wave");
@@ -1061,9 +1159,10 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     STAMP(8);
     // ---- prefetch: the records of step + 1 land in stg (LDS-DMA) while the dW1 tiles, the
     //      norm exchange and Adam run; every lane has read its rows of this step (sync #1).
-    //      The row split issues them with its partner exchange instead, behind the first
-    //      poll's loads: vmcnt retires in order, so the exchange loads would otherwise wait
-    //      for the gathers.
+    //      The row split issues them later: vmcnt retires in order, so its partner exchange's
+    //      loads would wait for the gathers.  The default protocol's fused kernels prepare them
+    //      under the first poll and issue them after sync #4; the other protocols issue them
+    //      behind the first poll's loads.
 #ifndef DDRL_ABL_NO_PREFETCH
     if (KSP == 1 && step + 1 < last) issue_rows<NW, ROWS>(U.rec, stride, cpr, cpr_l, inv_cpr_l, idxb, stg, U.R, ub.lds_bytes);
 #endif
@@ -1110,9 +1209,22 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
 #if DDRL_LX_ON
       if constexpr (LX) {
         float o4[4 * NQ];
+#ifdef DDRL_LX_ASMPOLL
+        // The early norm poll (xv) is consumed only by the exchange lane, after sync #4.  On the
+        // other waves the compiler would guard its registers at their next reuse (after sync #5),
+        // with a count that knows nothing of the gathers then in flight: a wait for HBM reads in
+        // front of Adam.  A use here retires it while nothing else is outstanding but the puts.
+        asm volatile("" : "+v"(xv));
+        // the gathers' index reads and addresses under the first poll's latency; the gathers
+        // themselves go out after sync #4
+        gx_get4c<NQ>(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + (gstep & 1)) * gx_box, lbit, o4, ub.err, st_stale, [&] {
+          rows_prepare<NW, ROWS>(G, U.rec, stride, cpr, cpr_l, inv_cpr_l, idxb, U.R);
+        });
+#else
         gx_get4<NQ>(lx_rsrc(ub.gx + ((gx_branch + (kq ^ 1)) * 2 + (gstep & 1)) * gx_box), lbit, o4, ub.err, [&] {
           if (step + 1 < last) issue_rows<NW, ROWS>(U.rec, stride, cpr, cpr_l, inv_cpr_l, idxb, stg, U.R, ub.lds_bytes);
         });
+#endif
         // both workgroups add the same two LSB-replaced partials
 #pragma unroll
         for (int k = 0; k < NSLOT; ++k) gs[k] = lx_t(gs[k], lbit) + o4[k];
@@ -1201,6 +1313,12 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     ss = wave_sum(ss);
     if (lane == 0) red[64 + w] = ss;
     __syncthreads();                                     // #4
+#ifdef DDRL_LX_ASMPOLL
+    // Row split: the records of step + 1 -> stg.  Waves 0 .. NW-2 only wait for the exchange
+    // lane until sync #5, so their gathers cost nothing here; they land under Adam.
+    if constexpr (LX)
+      if (step + 1 < last) rows_fire<NW, ROWS>(G, cpr_l, stg, ub.lds_bytes);
+#endif
     if (tid == xlane) {
       float local = 0.f;
       for (int i = 0; i < NW; ++i) local += red[64 + i];

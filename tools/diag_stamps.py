@@ -54,6 +54,14 @@ names = ["fwd", "loss", "dpp head/bias", "head bwd+db2+stores", "layer2 bwd+db1"
          "dW2 tiles (+out)", "sync#2", "X/dZ1 stores + sync#3", "prefetch issue", "dW1 tiles",
          "norm exchange", "adam", "sync#6", "partner exchange (split)"]
 print(f"steps {steps}, {dt / steps * 1e6:.2f} us/step wall")
+if hasattr(N.load(), "ddrl_diag_poll_stale"):
+    # first partner polls that missed, per wave (waves 0 .. 2 issue the record gathers behind the
+    # poll's loads; a re-poll queues behind them)
+    ps = (ctypes.c_uint * (32 * 8))()
+    assert N.load().ddrl_diag_poll_stale(ps) == 0
+    ps = np.array(ps, dtype=np.float64).reshape(32, 8)
+    for b in range(0, 32, 8):
+        print(f"block {b:2d}: first poll stale, waves 0-3: " + " ".join(f"{100 * x / steps:5.1f}%" for x in ps[b, :4]))
 for wg in range(len(blocks)):
     tot = a[wg].sum()
     print(f"{labels[wg]} WG: {tot:.0f} cycles/step")
