@@ -76,6 +76,24 @@ class EpisodeAccumulator:
         return int(sum(c == self.E for c in self.count))
 
 
+def scripted_done(T, n, seed=41, p=0.25):
+    """The seeded done pattern [T, n] of the scripted accounting tests."""
+    return (np.random.default_rng(seed).random((T, n)) < p).astype(np.uint8)
+
+
+def done_classes(done, E):
+    """How many envs of a done pattern fall into each class the accounting has to handle with a
+    quota of E episodes: never filling it (some without any episode), exactly E ends, more,
+    stepped after the quota is full, and the number of one-step episodes."""
+    done = np.asarray(done, bool)
+    T, n = done.shape
+    cnt = done.sum(0)
+    last_quota = np.array([np.flatnonzero(done[:, e])[E - 1] if cnt[e] >= E else T * 10 for e in range(n)])
+    one_step = sum(int(done[0, e]) + int((done[1:, e] & done[:-1, e]).sum()) for e in range(n))
+    return dict(never_fill=int((cnt < E).sum()), no_episode=int((cnt == 0).sum()), exactly=int((cnt == E).sum()),
+                more=int((cnt > E).sum()), stepped_after_quota=int((last_quota < T - 1).sum()), one_step=one_step)
+
+
 def eval_observe(orc, obs, filter_update):
     """OracleRollout._observe_block for evaluation: the env-side filter pushes only with
     filter_update, the per-policy filters normalize without update (compute_action)."""

@@ -9,9 +9,13 @@ from ddrl_amd import native as N
 from ddrl_amd.spec import make_cfg
 
 
-def make_ctx(env, n_envs, T, config=None, stream=None):
+def make_ctx(env, n_envs, T, config=None, stream=None, cfg_set=None):
+    """cfg_set: ddrl_cfg fields set on the cfg before the context is made (e.g. filter_update)."""
     import torch
     cfg, inst = make_cfg(env, n_envs, T, config)
+    for name, value in (cfg_set or {}).items():
+        assert hasattr(cfg, name), name
+        setattr(cfg, name, value)
     ctx = N.Context(cfg, 0, stream if stream is not None else torch.cuda.current_stream().cuda_stream)
     return ctx, cfg, inst
 
@@ -26,7 +30,8 @@ def policy_tables(cfg, inst):
     return out
 
 
-def init_params(ctx, cfg, seed, head_scale=30.0):
+def make_params(cfg, seed, head_scale=30.0):
+    """The seeded fcnet parameters of every policy (oracle dicts), heads scaled by head_scale."""
     rng = np.random.default_rng(seed)
     params = []
     for p in range(cfg.n_policies):
@@ -36,9 +41,14 @@ def init_params(ctx, cfg, seed, head_scale=30.0):
         pr["value_out/kernel"] *= head_scale
         pr["fc_1/bias"] += rng.normal(size=64).astype(np.float32) * 0.1
         pr["fc_out/bias"] += np.concatenate([np.zeros(A), -0.5 * np.ones(A)]).astype(np.float32)
-        shapes = O.ffn_param_shapes(cfg.obs_dim[p], 2 * A)
-        ctx.params_set(p, O.pack(pr, shapes))
         params.append(pr)
+    return params
+
+
+def init_params(ctx, cfg, seed, head_scale=30.0):
+    params = make_params(cfg, seed, head_scale)
+    for p, pr in enumerate(params):
+        ctx.params_set(p, O.pack(pr, O.ffn_param_shapes(cfg.obs_dim[p], 2 * cfg.act_dim)))
     return params
 
 
@@ -210,6 +220,19 @@ def run_rollout(ctx, cfg, inst, params, rng, filt, T, orc_cls=None, pfilt=None):
     norms = orc.gae()
     torch.cuda.synchronize()
     return orc, norms, np.stack(acts_gpu), np.stack(acts_orc)
+
+
+def oracle_rollout(cfg, inst, params, rng, filt, T):
+    """The oracle's half of run_rollout alone (no device): the same inputs from the same rng, the
+    oracle consuming its own actions.  Returns (oracle, eps)."""
+    obs, eps, fw, cfrc, done = synthetic_inputs(rng, cfg, T)
+    orc = OracleRollout(cfg, inst, params, filt)
+    for t in range(T):
+        orc.observe(obs[t])
+        orc.reward(t, fw[t], cfrc[t], orc.act(t, eps[t]), done[t])
+    orc.observe(obs[T])
+    orc.bootstrap()
+    return orc, eps
 
 
 # --------------------------------------------------------------------------------------

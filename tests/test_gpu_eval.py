@@ -163,8 +163,7 @@ def _scripted(cfg, T, n, seed=43):
     _, _, fw, cfrc, _ = synthetic_inputs(rng, cfg, T)
     actions = rng.uniform(-1.0, 1.0, size=(T, n, 8)).astype(np.float32)
     kin = rng.normal(size=(T, n, 9)).astype(np.float32)
-    done = (np.random.default_rng(41).random((T, n)) < 0.25).astype(np.uint8)
-    return fw, cfrc, actions, kin, done
+    return fw, cfrc, actions, kin, R.scripted_done(T, n)
 
 
 def _run_scripted(ctx, cfg, inst, E, inputs, filter_update=False):
@@ -198,12 +197,26 @@ def test_scripted_done_pattern_covers_every_class():
                                       pytest.param(19, {"env_config": {"global_reward": True}}, id="global19"),
                                       pytest.param(19, {"env_config": {"norm_reward": True}}, id="norm19")])
 def test_episode_accounting_scripted(n, config):
+    _episode_accounting(n, config, 37)
+
+
+@pytest.mark.parametrize("n,config", [pytest.param(64, None, id="per_leg64"),      # one exactly full block
+                                      pytest.param(70, None, id="per_leg70"),      # two blocks, clamped tail lanes
+                                      pytest.param(64, {"env_config": {"global_reward": True}}, id="global64"),
+                                      pytest.param(70, {"env_config": {"norm_reward": True}}, id="norm70")])
+def test_episode_accounting_multi_block(n, config):
+    """k_eval_accum over more than its first block (64 envs x 4 lanes): inputs generated at n, whose
+    done pattern tests/test_rollout_edge_inputs.py guards."""
+    _episode_accounting(n, config, n)
+
+
+def _episode_accounting(n, config, n_inputs):
     ctx, cfg, inst = _ctx("QuantrupedMultiEnv_Local", n, 4, config)
     mode = {None: N.REWARD_PER_LEG, "global_reward": N.REWARD_GLOBAL, "norm_reward": N.REWARD_NORM}[
         next(iter(config["env_config"])) if config else None]
     assert cfg.reward_mode == mode
     E, T = 2, 12
-    inputs = _scripted(cfg, T, 37)
+    inputs = _scripted(cfg, T, n_inputs)
     inputs = tuple(a[:, :n] for a in inputs)
     table, progress, ref = _run_scripted(ctx, cfg, inst, E, inputs)
     assert table.shape == (n, E, 6) and table.dtype == np.float64
