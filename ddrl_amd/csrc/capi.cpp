@@ -127,6 +127,14 @@ struct ddrl_ctx {
   float* ev_kin = nullptr;
   int ev_table_E = 0;
   int ev_normc_ok = 0;
+  // input sensitivity (ddrl_eval_sens_*): the steps [P][DDRL_MAXD], per policy the per-base-row
+  // accumulators [C][2][d][A] and step counts [C], the reduced result; sens_act_ok: a
+  // ddrl_eval_act has run since the filter constants may last have changed
+  int sens_on = 0, sens_act_ok = 0;
+  double* sens_step = nullptr;
+  double* sens_acc[DDRL_MAXP] = {nullptr};
+  long long* sens_cnt[DDRL_MAXP] = {nullptr};
+  double* sens_red = nullptr;      // [2 * DDRL_MAXD * 8] + one int64
   std::vector<void*> allocs;
 };
 
@@ -558,6 +566,7 @@ int ddrl_filter_set(ddrl_ctx* c, double n, const double* M, const double* S) {
   HIPCHK(hipMemcpyAsync(c->f_S, S, D * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   c->ev_normc_ok = 0;
+  c->sens_act_ok = 0;
   return 0;
 }
 
@@ -654,6 +663,7 @@ int ddrl_observe_range(ddrl_ctx* c, const float* obs, int e0, int e1) {
   ra.N = n;
   ra.e0 = e0;
   c->ev_normc_ok = 0;
+  c->sens_act_ok = 0;
   launch_filter_push(c->stream, obs_r, n, g.obs_full_dim, c->f_n, c->f_M, c->f_S, c->f_normc,
                      g.filter_update, g.filter_enabled, c->f_dn, c->f_dM, c->f_dS, c->f_part);
   const float clip = g.filter_enabled ? g.filter_clip : 0.f;
@@ -951,6 +961,8 @@ int ddrl_eval_begin(ddrl_ctx* c, const ddrl_eval_cfg* ec) {
   HIPCHK(hipMemsetAsync(c->ev_table, 0xFF, N * E * 6 * 8, c->stream));   // all-ones doubles: NaN rows
   c->ev_cfg = *ec;
   c->ev_normc_ok = 0;
+  c->sens_on = 0;
+  c->sens_act_ok = 0;
   c->ev_on = 1;
   return 0;
 }
@@ -985,6 +997,7 @@ int ddrl_eval_act(ddrl_ctx* c, const float* obs, const float* eps, float* action
   ra.e0 = 0;
   launch_eval_act(c->stream, ra, ea);
   HIPCHK(hipGetLastError());
+  c->sens_act_ok = 1;
   return 0;
 }
 
@@ -1029,6 +1042,96 @@ int ddrl_eval_end(ddrl_ctx* c) {
   CHK_EVAL(c);
   HIPCHK(hipStreamSynchronize(c->stream));
   c->ev_on = 0;
+  c->sens_on = 0;
+  return 0;
+}
+
+// ---- input sensitivity (eval_sens.hip) ---------------------------------------------------
+int ddrl_eval_sens_begin(ddrl_ctx* c, const double* const* step_host) {
+  CHK_EVAL(c);
+  if (c->cfg.model_kind != DDRL_MODEL_FFN) return fail("sensitivity: fcnet models only");
+  if (!step_host) return fail("sensitivity: null step array");
+  const ddrl_cfg& g = c->cfg;
+  std::vector<double> steps((size_t)DDRL_MAXP * DDRL_MAXD, 0.0);
+  for (int p = 0; p < g.n_policies; ++p) {
+    if (!step_host[p]) return fail("sensitivity: null step array");
+    for (int f = 0; f < c->pol[p].d; ++f) {
+      const double h = step_host[p][f];
+      if (!(h >= 0.0) || !(h <= 1.7976931348623157e308)) return fail("sensitivity: steps must be finite and >= 0");
+      steps[(size_t)p * DDRL_MAXD + f] = h;
+    }
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((!c->sens_step && dalloc(c, &c->sens_step, steps.size())) ||
+      (!c->sens_red && dalloc(c, &c->sens_red, 2 * DDRL_MAXD * 8 + 1)))
+    return -1;
+  for (int p = 0; p < g.n_policies; ++p) {
+    const Policy& P = c->pol[p];
+    if ((!c->sens_acc[p] && dalloc(c, &c->sens_acc[p], (size_t)P.C * 2 * P.d * g.act_dim)) ||
+        (!c->sens_cnt[p] && dalloc(c, &c->sens_cnt[p], P.C)))
+      return -1;
+  }
+  HIPCHK(hipMemcpyAsync(c->sens_step, steps.data(), steps.size() * 8, hipMemcpyHostToDevice, c->stream));
+  for (int p = 0; p < g.n_policies; ++p) {
+    const Policy& P = c->pol[p];
+    HIPCHK(hipMemsetAsync(c->sens_acc[p], 0, (size_t)P.C * 2 * P.d * g.act_dim * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->sens_cnt[p], 0, (size_t)P.C * 8, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));   // `steps` is read until here
+  c->sens_on = 1;
+  return 0;
+}
+
+#define CHK_SENS(c)                                    \
+  do {                                                 \
+    CHK_EVAL(c);                                       \
+    if (!(c)->sens_on) return fail("sensitivity: call ddrl_eval_sens_begin first"); \
+  } while (0)
+
+int ddrl_eval_sens(ddrl_ctx* c, const float* obs, float* const* means_out) {
+  CHK_SENS(c);
+  if (!obs) return fail("null observation buffer");
+  if (!c->sens_act_ok)
+    return fail("sensitivity: call ddrl_eval_act on this observation first (the filter constants may have changed)");
+  const ddrl_cfg& g = c->cfg;
+  EvalSensArgs sa{};
+  for (int p = 0; p < g.n_policies; ++p) {
+    const Policy& P = c->pol[p];
+    sa.theta[p] = P.theta;
+    sa.cup[p] = g.leg_coupling ? P.theta + ffn_param_count(P.d, g.act_dim) : nullptr;
+    sa.means_out[p] = means_out ? means_out[p] : nullptr;
+    sa.acc[p] = c->sens_acc[p];
+    sa.rowcnt[p] = c->sens_cnt[p];
+  }
+  sa.obs = obs; sa.normc = c->f_normc; sa.pf = g.policy_filter ? c->pf : nullptr;
+  sa.clip = g.filter_enabled ? g.filter_clip : 0.f;
+  sa.step = c->sens_step; sa.ep_count = c->ev_count; sa.E = c->ev_cfg.episodes_per_env;
+  // one base row per workgroup up to 512 rows per policy, a loop over base rows past that (the
+  // measured choice, DESIGN.md "Sensitivity"); DDRL_SENS_GRID (read at every launch) moves the cap
+  int cap = 512;
+  if (const char* e = std::getenv("DDRL_SENS_GRID")) cap = std::max(1, std::atoi(e));
+  RouteArgs ra = c->route;
+  ra.e0 = 0;
+  launch_eval_sens(c->stream, ra, sa, cap);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ddrl_eval_sens_results(ddrl_ctx* c, int policy, double* grads, double* grads_abs, int64_t* rows) {
+  CHK_SENS(c);
+  if (policy < 0 || policy >= c->cfg.n_policies) return fail("bad policy id");
+  if (!grads || !grads_abs || !rows) return fail("null sensitivity output");
+  const Policy& P = c->pol[policy];
+  const int n = P.d * c->cfg.act_dim;
+  long long* rows_dev = reinterpret_cast<long long*>(c->sens_red + 2 * DDRL_MAXD * 8);
+  launch_sens_reduce(c->stream, c->sens_acc[policy], c->sens_cnt[policy], P.C, 2 * n, c->sens_red, rows_dev);
+  HIPCHK(hipGetLastError());
+  long long r = 0;
+  HIPCHK(hipMemcpyAsync(grads, c->sens_red, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(grads_abs, c->sens_red + n, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&r, rows_dev, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *rows = (int64_t)r;
   return 0;
 }
 
@@ -1051,6 +1154,7 @@ int ddrl_eval_hostenv(ddrl_ctx* c, ddrl_hostenv* env, const float* eps_dev, int 
   int t = 0;
   for (; t < limit && !rc;) {
     rc = ddrl_eval_act(c, c->h_obs, eps_dev ? eps_dev + (size_t)t * eps_step : nullptr, c->h_act, nullptr);
+    if (!rc && c->sens_on) rc = ddrl_eval_sens(c, c->h_obs, nullptr);
     if (!rc && hipMemcpyAsync(env->act, c->h_act, N * 8 * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
       rc = fail("D2H copy failed");
     // the actions are on the host, and the previous step's H2D copies have left the pinned buffers

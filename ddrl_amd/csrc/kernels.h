@@ -127,6 +127,27 @@ struct EvalAccumArgs {
 void launch_eval_accum(hipStream_t s, const RewardArgs& ra, const EvalAccumArgs& ev, const float* fw,
                        const float* cfrc, const float* actions, const float* kin, const uint8_t* done);
 
+// ---- input sensitivity of the evaluated policies (eval_sens.hip) ----
+struct EvalSensArgs {
+  const float* theta[DDRL_MAXP];
+  const float* cup[DDRL_MAXP];     // "cup" leg-coupling table [4][A] (nullptr: none)
+  float* means_out[DDRL_MAXP];     // optional [C_p][2 d][A] clipped means of the perturbed rows (nullptr)
+  double* acc[DDRL_MAXP];          // [C_p][2][d][A]: per base row, sum of (plus - minus) and of its magnitude
+  long long* rowcnt[DDRL_MAXP];    // [C_p] steps accumulated per base row
+  const float* obs;                // raw observations [N][full_dim]
+  const double* normc;             // env-side filter constants, as the step's ddrl_eval_act read them
+  const double* pf;                // per-policy filter state (PF_* layout) or nullptr
+  float clip;
+  const double* step;              // [P][DDRL_MAXD] perturbation h_f of the env-normalized input
+  const int32_t* ep_count;         // [N] episodes recorded per env (the quota gate)
+  int E;
+};
+// grid_cap: most workgroups per policy; a workgroup loops over base rows when there are more
+void launch_eval_sens(hipStream_t s, const RouteArgs& ra, const EvalSensArgs& sa, int grid_cap);
+// out[n] = sum over the C rows, in row order, of acc[C][n]; rows[0] = sum of rowcnt[C]
+void launch_sens_reduce(hipStream_t s, const double* acc, const long long* rowcnt, int C, int n, double* out,
+                        long long* rows);
+
 // ---- GAE + standardization statistics ----
 struct GaeArgs {
   float* rec; RecLayout lay; int C, T, N, k;

@@ -9,6 +9,9 @@ stand-in env has no terrain: `hf_smoothness` is carried into the rows as a label
 from __future__ import annotations
 
 import csv
+import os
+
+import numpy as np
 
 COLUMNS = ["approach", "seed", "trained_on", "evaluated_on", "simulation_run", "reward", "duration", "distance",
            "power", "velocity", "CoT"]   # evaluate_trained_policies_pd.py:69
@@ -28,6 +31,41 @@ def rollout_episodes(env, agent, num_episodes=1, num_steps=1000, render=False, e
     explore = True if explore_during_rollout is None else bool(explore_during_rollout)
     return agent.evaluate(num_episodes=num_episodes, num_steps=num_steps, explore=explore, tvel=tvel,
                           **evaluate_args)
+
+
+def default_sens_steps(n, S, rel_step=0.1, M=None):
+    """The reference's perturbation steps (rollout_episodes_compute_gradient.py:62-66):
+    rel_step * rs.std of a MeanStdFilter's RunningStat (n, M, S), std = sqrt(S / (n - 1)); while
+    n <= 1 RLlib's RunningStat reports var = M^2 (0 when M is not given)."""
+    S = np.asarray(S, np.float64)
+    if n > 1:
+        std = np.sqrt(S / (n - 1))
+    else:
+        std = np.abs(np.asarray(M, np.float64)) if M is not None else np.zeros_like(S)
+    return float(rel_step) * std
+
+
+def rollout_episodes_compute_gradient(env, agent, num_episodes=1, num_steps=1000, render=False, experiment_nr=0,
+                                      tag="tvel1", out_dir=".", **evaluate_args):
+    """rollout_episodes(env, agent, ...) of the reference's
+    evaluation/rollout_episodes_compute_gradient.py:39-170 (driver:
+    evaluation/generate_manual_gradients_targetvel.py): the evaluation episodes plus the importance
+    matrix, written as grads_<tag>_<nr>.npy and grads_<tag>_abs_<nr>.npy ([d, A] float64, the files
+    visualization/visualize_evaluated_grads_centralized.py reads) into out_dir.  The two files hold
+    the first policy's matrices (the reference's central_policy); with several policies every
+    policy also gets grads_<tag>_<nr>_<policy_id>.npy / grads_<tag>_abs_<nr>_<policy_id>.npy.
+    `agent` is a ddrl_amd PPOTrainer; `env` is accepted for the signature.  evaluate_args go to
+    PPOTrainer.evaluate_sensitivity (rel_step, steps, tvel, n_envs, env_filter, seed, explore).
+    Returns (reward_eps, steps_eps, dist_eps, power_total_eps, vel_eps, cot_eps)."""
+    if render:
+        raise NotImplementedError("rendering is out of scope: the host env plane has no viewer")
+    lists, sens = agent.evaluate_sensitivity(num_episodes=num_episodes, num_steps=num_steps, **evaluate_args)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, (pid, res) in enumerate(sens.items()):
+        for suffix in ([""] if k == 0 else []) + ([f"_{pid}"] if len(sens) > 1 else []):
+            np.save(os.path.join(out_dir, f"grads_{tag}_{experiment_nr}{suffix}.npy"), res["grads"])
+            np.save(os.path.join(out_dir, f"grads_{tag}_abs_{experiment_nr}{suffix}.npy"), res["grads_abs"])
+    return lists
 
 
 def evaluate_checkpoints(config, checkpoint_paths, approach, hf_smoothness=1.0, num_episodes=100, num_steps=1000,

@@ -135,6 +135,9 @@ _SIGS = {
     "ddrl_eval_results": ([VP, VP, C.c_size_t], C.c_int),
     "ddrl_eval_end": ([VP], C.c_int),
     "ddrl_eval_hostenv": ([VP, VP, VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
+    "ddrl_eval_sens_begin": ([VP, C.POINTER(VP)], C.c_int),
+    "ddrl_eval_sens": ([VP, VP, C.POINTER(VP)], C.c_int),
+    "ddrl_eval_sens_results": ([VP, C.c_int, VP, VP, C.POINTER(C.c_int64)], C.c_int),
 }
 
 _lib = None
@@ -517,6 +520,36 @@ class Context:
         _ck(self.lib.ddrl_eval_hostenv(self.h, env.h, _ptr(eps_dev), int(eps_steps), int(max_steps), int(poll_every),
                                        C.byref(n)))
         return int(n.value)
+
+    # ---- input sensitivity of the evaluated policies (between eval_begin and eval_end) ----
+    def eval_sens_begin(self, steps):
+        """steps: per policy the perturbation h_f of each env-normalized input, obs_dim[p] finite
+        values >= 0.  Clears the accumulators; eval_hostenv then runs eval_sens at every step."""
+        if steps is None or len(steps) != self.cfg.n_policies:
+            raise ValueError(f"steps: one array per policy ({self.cfg.n_policies})")
+        arrs = []
+        for p, s in enumerate(steps):
+            a = np.ascontiguousarray(s, np.float64).reshape(-1)
+            if a.size != self.cfg.obs_dim[p]:
+                raise ValueError(f"steps[{p}]: {a.size} values, the policy takes {self.cfg.obs_dim[p]}")
+            arrs.append(a)
+        tab = (VP * MAX_P)(*[arrs[p].ctypes.data if p < len(arrs) else None for p in range(MAX_P)])
+        _ck(self.lib.ddrl_eval_sens_begin(self.h, tab))
+
+    def eval_sens(self, obs_dev, means_out=None):
+        """After eval_act of the same observations, before eval_step.  means_out: per policy a
+        device buffer [C_p][2 d][A] (float32) or None."""
+        mo = None
+        if means_out is not None:
+            mo = (VP * MAX_P)(*[_ptr(means_out[p]) if p < len(means_out) else None for p in range(MAX_P)])
+        _ck(self.lib.ddrl_eval_sens(self.h, _ptr(obs_dev), mo))
+
+    def eval_sens_results(self, pid):
+        """(grads [d, A], grads_abs [d, A], rows) of policy pid; synchronizes."""
+        d, A = (self.cfg.obs_dim[pid], self.cfg.act_dim) if 0 <= pid < self.cfg.n_policies else (1, 1)
+        g, ga, rows = np.zeros((d, A)), np.zeros((d, A)), C.c_int64()
+        _ck(self.lib.ddrl_eval_sens_results(self.h, int(pid), g.ctypes.data, ga.ctypes.data, C.byref(rows)))
+        return g, ga, int(rows.value)
 
     def policy_forward(self, pid, obs_dev, n, logits_dev, values_dev, node_dev=None):
         _ck(self.lib.ddrl_policy_forward(self.h, pid, _ptr(obs_dev), _ptr(node_dev), n,

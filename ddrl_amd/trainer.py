@@ -498,6 +498,12 @@ class PPOTrainer:
         evaluation process gets).  The per-policy filters are applied without updates, as RLlib's
         compute_action does.  The training context, its env backend and the noise generator are
         not touched: evaluation runs on its own context, env plane and generator (`seed`)."""
+        return self._evaluate(num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed)[0]
+
+    def _evaluate(self, num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed, sens_steps=None):
+        """The body of evaluate / evaluate_sensitivity: (six lists, per-policy sensitivity results or
+        None).  sens_steps: a function of the evaluation context returning the per-policy steps;
+        with it, the C++ loop runs the sensitivity kernel after every action."""
         if env_filter not in ("continue", "frozen", "fresh"):
             raise ValueError(f"env_filter {env_filter!r}: 'continue', 'frozen' or 'fresh'")
         if self.cfg.model_kind != N.MODEL_FFN:
@@ -526,14 +532,59 @@ class PPOTrainer:
                 gen.manual_seed(seed + 1)
                 eps = torch.randn((max_steps, n_envs, cfg.n_agents, cfg.act_dim), device=self.device, generator=gen)
             ectx.eval_begin(E, filter_update=env_filter != "frozen")
+            if sens_steps is not None:
+                ectx.eval_sens_begin(sens_steps(ectx))
             ectx.eval_hostenv(henv, eps, max_steps if explore else 0, max_steps, poll_every=min(25, num_steps))
             rows = ectx.eval_results().reshape(-1, 6)
+            sens = None
+            if sens_steps is not None:
+                sens = {}
+                for p, pid in enumerate(self.policy_ids):
+                    g, ga, n = ectx.eval_sens_results(p)
+                    sens[pid] = {"grads": g, "grads_abs": ga, "rows": n}
             ectx.eval_end()
         finally:
             henv.close()
         rows = rows[~np.isnan(rows[:, 1])][:num_episodes]
         reward, steps, dist, power, vel, cot = (rows[:, i].tolist() for i in range(6))
-        return reward, [int(s) for s in steps], dist, power, vel, cot
+        return (reward, [int(s) for s in steps], dist, power, vel, cot), sens
+
+    def evaluate_sensitivity(self, num_episodes=10, num_steps=1000, rel_step=0.1, steps=None, tvel=None, n_envs=None,
+                             env_filter="continue", seed=0, explore=True):
+        """evaluate() plus the importance matrix of the reference's
+        evaluation/rollout_episodes_compute_gradient.py:59-68, :111-122: at every control step every
+        input of every policy row is moved by -h_f / +h_f and the difference of the clipped action
+        means (explore=False) is summed into grads[f][j], its magnitude into grads_abs[f][j] (fp64),
+        over the steps of exactly the episodes of the result lists (an env stops contributing when
+        its quota is full).  Returns (six lists, {policy_id: {"grads": [d, A], "grads_abs": [d, A],
+        "rows": int}}); the six lists are evaluate()'s for the same arguments.
+
+        Steps: with the per-policy filter (observation_filter: MeanStdFilter) h_f = rel_step * std_f,
+        std_f = sqrt(S_f / (n - 1)) of that filter, as the reference's 0.1 * rs.std.  Without it
+        (an extension: the reference only runs the filtered centralized policy) h_f = rel_step * 1.0,
+        the env-normalized columns having unit scale.  `steps` ({policy_id: [d]} or a per-policy
+        list) overrides both.  Every policy of every architecture gets a matrix; constant inputs
+        (the LegID one-hot) are not moved and their rows stay zero."""
+        from .evaluation import default_sens_steps
+
+        def sens_steps(ectx):
+            out = []
+            for p, pid in enumerate(self.policy_ids):
+                d = int(self.cfg.obs_dim[p])
+                given = None if steps is None else (steps.get(pid) if isinstance(steps, dict) else steps[p])
+                if given is not None:
+                    h = np.asarray(given, np.float64).reshape(-1)
+                    if h.size != d:
+                        raise ValueError(f"steps for {pid!r}: {h.size} values, the policy takes {d}")
+                elif self.cfg.policy_filter:
+                    n, M, S = ectx.policy_filter_get(p)
+                    h = default_sens_steps(n, S, rel_step, M)
+                else:
+                    h = np.full(d, float(rel_step))
+                out.append(h)
+            return out
+
+        return self._evaluate(num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed, sens_steps)
 
     def compute_action(self, obs, policy_id=None, explore=None, seed=None, agent_id=None):
         """Trainer.compute_action for one agent observation (the policy's input row, as the env

@@ -259,6 +259,27 @@ int ddrl_eval_end(ddrl_ctx* ctx);
  * steps_run (may be NULL): env steps taken. */
 int ddrl_eval_hostenv(ddrl_ctx* ctx, ddrl_hostenv* env, const float* eps_dev, int eps_steps, int max_steps,
                       int poll_every, int* steps_run);
+/* Input sensitivity ("importance matrix") of the evaluated policies
+ * (evaluation/rollout_episodes_compute_gradient.py:59-68, :111-122, :167-168): at every step, every
+ * non-constant input feature f of every (env, slot) row is moved by -h_f and +h_f, the 2d perturbed
+ * rows go through the policy forward, and mean_plus - mean_minus (clipped action means in the
+ * policy's own action order, subtracted in fp32) is added in fp64 into grads[f][j], its magnitude
+ * into grads_abs[f][j].  h_f is added to the env-normalized input in fp64, before the per-policy
+ * filter and the rounding to fp32.  Constant inputs (the LegID one-hot) are skipped: their rows
+ * stay zero.  An env contributes while it is below its episode quota, so the matrices describe
+ * the episodes of the result table.  Deterministic (no floating-point atomics): the same calls
+ * give the same bits.  Writes no record, filter, Adam state or parameter.
+ *   eval_sens_begin: after eval_begin; step_host[p] = obs_dim[p] finite doubles >= 0; allocates and
+ *     clears the accumulators.  eval_end (and the next eval_begin) ends the mode;
+ *   eval_sens: after eval_act of the same obs_dev and before eval_step; means_out_dev (NULL, or a
+ *     host array of n_policies device pointers, entries may be NULL) receives the clipped means
+ *     [C_p][2 d][A] of the perturbed rows (row 2f: minus, 2f + 1: plus; NaN for constant inputs);
+ *   eval_sens_results: synchronizes, sums over rows in a fixed order; grads / grads_abs are
+ *     [obs_dim][A] doubles on the host, rows the (env, slot) rows accumulated over all steps.
+ * With the mode on, ddrl_eval_hostenv issues eval_sens after every eval_act. */
+int ddrl_eval_sens_begin(ddrl_ctx* ctx, const double* const* step_host);
+int ddrl_eval_sens(ddrl_ctx* ctx, const float* obs_dev, float* const* means_out_dev);
+int ddrl_eval_sens_results(ddrl_ctx* ctx, int policy, double* grads, double* grads_abs, int64_t* rows);
 
 /* Postprocessing: GAE over the fragment for every policy + advantage standardization
  * statistics (a11/a12). */
