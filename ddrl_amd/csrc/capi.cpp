@@ -135,6 +135,15 @@ struct ddrl_ctx {
   double* sens_acc[DDRL_MAXP] = {nullptr};
   long long* sens_cnt[DDRL_MAXP] = {nullptr};
   double* sens_red = nullptr;      // [2 * DDRL_MAXD * 8] + one int64
+  // episode accounting (ddrl_episodes_*), allocated by the first call: the in-flight state of
+  // every env (interleaved total, per-agent totals, length), the per-(step, wave) counts and
+  // their scan, the table of the last collect (ep_cap rows of 8 doubles, ep_rows written);
+  // ep_collected: the fragment the context holds has been walked (rewards / records re-arm it)
+  double *ep_total = nullptr, *ep_agent = nullptr, *ep_table = nullptr;
+  int *ep_len = nullptr, *ep_cnt = nullptr;
+  long long *ep_base = nullptr, *ep_word = nullptr;
+  long long ep_cap = 0, ep_rows = -1;
+  int ep_collected = 0;
   std::vector<void*> allocs;
 };
 
@@ -766,6 +775,7 @@ int ddrl_reward_range(ddrl_ctx* c, int t, int e0, int e1, const float* fw, const
   RewardArgs ra = make_reward(c);
   ra.e0 = e0; ra.n = e1 - e0;
   ra.t = t;
+  c->ep_collected = 0;
   launch_reward(c->stream, ra, fw, cfrc, actions, done, c->done_tn);
   HIPCHK(hipGetLastError());
   return 0;
@@ -822,6 +832,7 @@ int ddrl_rollout_fragment(ddrl_ctx* c, const float* obs, const float* eps, const
     std::copy(key, key + 6, c->rg_key);
   }
   HIPCHK(hipGraphLaunch(c->rg_exec, c->stream));
+  c->ep_collected = 0;
   return 0;
 }
 
@@ -1175,6 +1186,95 @@ int ddrl_eval_hostenv(ddrl_ctx* c, ddrl_hostenv* env, const float* eps_dev, int 
   if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("stream synchronize failed");
   if (steps_run) *steps_run = t;
   return rc ? -1 : 0;
+}
+
+// ---- episode accounting of the training rollout (episodes.hip) ---------------------------
+// Nothing here writes a record, done_tn, last_v, a filter, Adam state or a parameter.
+static int ep_state(ddrl_ctx* c) {
+  if (c->ep_total) return 0;
+  const size_t N = c->cfg.n_envs, TW = (size_t)c->cfg.frag_len * ((N + 63) / 64);
+  return dalloc(c, &c->ep_total, N) || dalloc(c, &c->ep_agent, N * DDRL_MAXAG) || dalloc(c, &c->ep_len, N) ||
+         dalloc(c, &c->ep_cnt, TW) || dalloc(c, &c->ep_base, TW) || dalloc(c, &c->ep_word, 1);
+}
+
+int ddrl_episodes_collect(ddrl_ctx* c, int64_t* n_finished) {
+  CHK_CTX(c);
+  if (!n_finished) return fail("episodes: null count output");
+  if (c->ep_collected)
+    return fail("episodes: this fragment has been collected (collect once per fragment, after its last reward)");
+  if (ep_state(c)) return -1;
+  const ddrl_cfg& g = c->cfg;
+  const RewardArgs ra = make_reward(c);
+  EpArgs a{};
+  for (int p = 0; p < g.n_policies; ++p) { a.rec[p] = ra.rec[p]; a.lay[p] = ra.lay[p]; a.k[p] = ra.k[p]; }
+  for (int j = 0; j < g.n_agents; ++j) {
+    a.policy_of_agent[j] = ra.policy_of_agent[j];
+    a.slot_of_agent[j] = ra.slot_of_agent[j];
+  }
+  a.N = g.n_envs; a.T = g.frag_len; a.n_agents = g.n_agents; a.W = (g.n_envs + 63) / 64;
+  a.done_tn = c->done_tn; a.cnt = c->ep_cnt; a.base = c->ep_base; a.total = c->ep_word;
+  a.ep_total = c->ep_total; a.ep_agent = c->ep_agent; a.ep_len = c->ep_len;
+  launch_ep_count_scan(c->stream, a);
+  HIPCHK(hipGetLastError());
+  long long total = 0;
+  HIPCHK(hipMemcpyAsync(&total, c->ep_word, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));   // the one synchronize: nothing in flight reads the table either
+  if (total < 0 || total > (long long)g.frag_len * g.n_envs) return fail("episodes: bad episode count");
+  if (total > c->ep_cap) {
+    const long long cap = std::max(total, 2 * c->ep_cap);
+    dfree(c, &c->ep_table);
+    c->ep_cap = 0;
+    c->ep_rows = -1;
+    if (dalloc(c, &c->ep_table, (size_t)cap * 8)) return -1;
+    c->ep_cap = cap;
+  }
+  a.table = c->ep_table; a.cap = c->ep_cap;
+  launch_ep_walk(c->stream, a);
+  HIPCHK(hipGetLastError());
+  c->ep_collected = 1;
+  c->ep_rows = total;
+  *n_finished = (int64_t)total;
+  return 0;
+}
+
+int ddrl_episodes_rows(ddrl_ctx* c, double* host, size_t n_rows) {
+  CHK_CTX(c);
+  if (!host) return fail("episodes: null rows buffer");
+  if (c->ep_rows < 0) return fail("episodes: call ddrl_episodes_collect first");
+  if (n_rows != (size_t)c->ep_rows) return fail("episodes: n_rows differs from the last collect's count");
+  if (n_rows) HIPCHK(hipMemcpyAsync(host, c->ep_table, n_rows * 8 * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int ddrl_episodes_inflight(ddrl_ctx* c, double* host, size_t n_envs) {
+  CHK_CTX(c);
+  if (!host) return fail("episodes: null in-flight buffer");
+  const size_t N = c->cfg.n_envs;
+  if (n_envs != N) return fail("episodes: the in-flight state has n_envs rows");
+  if (ep_state(c)) return -1;
+  std::vector<double> tot(N), ag(N * DDRL_MAXAG);
+  std::vector<int> len(N);
+  HIPCHK(hipMemcpyAsync(tot.data(), c->ep_total, N * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(ag.data(), c->ep_agent, N * DDRL_MAXAG * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(len.data(), c->ep_len, N * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (size_t e = 0; e < N; ++e) {
+    host[e * 6] = tot[e];
+    for (int j = 0; j < DDRL_MAXAG; ++j) host[e * 6 + 1 + j] = ag[e * DDRL_MAXAG + j];
+    host[e * 6 + 5] = (double)len[e];
+  }
+  return 0;
+}
+
+int ddrl_episodes_reset(ddrl_ctx* c) {
+  CHK_CTX(c);
+  if (!c->ep_total) return 0;   // nothing in flight yet
+  const size_t N = c->cfg.n_envs;
+  HIPCHK(hipMemsetAsync(c->ep_total, 0, N * 8, c->stream));
+  HIPCHK(hipMemsetAsync(c->ep_agent, 0, N * DDRL_MAXAG * 8, c->stream));
+  HIPCHK(hipMemsetAsync(c->ep_len, 0, N * 4, c->stream));
+  return 0;
 }
 
 int ddrl_gae(ddrl_ctx* c) {
@@ -1621,6 +1721,7 @@ int ddrl_records_set(ddrl_ctx* c, int pid, const float* host, size_t n) {
   if (n != (size_t)P.R * P.lay.stride) return fail("record buffer size mismatch");
   HIPCHK(hipMemcpyAsync(P.rec, host, n * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->ep_collected = 0;
   return 0;
 }
 

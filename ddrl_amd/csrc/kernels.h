@@ -163,6 +163,24 @@ __host__ __device__ inline int gae_partials_len(int C) { return gae_wave_base(C)
 struct GaeBatch { GaeArgs g[DDRL_MAXP]; int P; };
 void launch_gae(hipStream_t s, const GaeBatch& gb);   // every policy of the context, one launch
 
+// ---- episode accounting of the training rollout (episodes.hip) ----
+struct EpArgs {
+  const float* rec[DDRL_MAXP]; RecLayout lay[DDRL_MAXP]; int k[DDRL_MAXP];
+  int policy_of_agent[DDRL_MAXAG], slot_of_agent[DDRL_MAXAG];
+  int N, T, n_agents, W;           // W = ceil(N / 64) waves of envs
+  const uint8_t* done_tn;
+  int* cnt;                        // [T][W] episodes finished per (step, wave)
+  long long* base;                 // [T][W] exclusive scan of cnt in (t, w) order
+  long long* total;                // [1] sum of cnt
+  double* ep_total;                // in-flight state of every env: [N] interleaved total,
+  double* ep_agent;                //   [N][DDRL_MAXAG] per-agent totals,
+  int* ep_len;                     //   [N] env steps
+  double* table;                   // [cap][8]: {t, env, length, total, agent_0 .. agent_3}
+  long long cap;
+};
+void launch_ep_count_scan(hipStream_t s, const EpArgs& a);   // cnt, base, total
+void launch_ep_walk(hipStream_t s, const EpArgs& a);         // table rows + the in-flight state
+
 // ---- PPO update (fused persistent minibatch loop) ----
 struct UpdateArgs {
   const float* rec; RecLayout lay;

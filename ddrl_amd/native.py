@@ -53,6 +53,7 @@ class DdrlEvalCfg(C.Structure):
 
 TOTAL_MASS = 8.78710174560547   # mj_getTotalmass of the QuAntruped model (rollout_episodes.py:152)
 EVAL_COLUMNS = ("reward", "steps", "distance", "power", "velocity", "cot")
+EPISODE_COLUMNS = ("t", "env", "length", "total", "agent_0", "agent_1", "agent_2", "agent_3")
 
 VP = C.c_void_p
 _SIGS = {
@@ -138,6 +139,10 @@ _SIGS = {
     "ddrl_eval_sens_begin": ([VP, C.POINTER(VP)], C.c_int),
     "ddrl_eval_sens": ([VP, VP, C.POINTER(VP)], C.c_int),
     "ddrl_eval_sens_results": ([VP, C.c_int, VP, VP, C.POINTER(C.c_int64)], C.c_int),
+    "ddrl_episodes_collect": ([VP, C.POINTER(C.c_int64)], C.c_int),
+    "ddrl_episodes_rows": ([VP, VP, C.c_size_t], C.c_int),
+    "ddrl_episodes_inflight": ([VP, VP, C.c_size_t], C.c_int),
+    "ddrl_episodes_reset": ([VP], C.c_int),
 }
 
 _lib = None
@@ -392,6 +397,27 @@ class Context:
 
     def gae(self):
         _ck(self.lib.ddrl_gae(self.h))
+
+    # ---- episode accounting of the training rollout ----
+    def episodes_collect(self):
+        """The episodes that finished in the fragment the context holds, float64 [n, 8] rows
+        (EPISODE_COLUMNS) in ascending (t, env) order; agents the env does not have are NaN.
+        Once per fragment, after its last reward; advances the in-flight state of every env."""
+        n = C.c_int64()
+        _ck(self.lib.ddrl_episodes_collect(self.h, C.byref(n)))
+        a = np.empty((int(n.value), 8), np.float64)
+        _ck(self.lib.ddrl_episodes_rows(self.h, a.ctypes.data, a.shape[0]))
+        return a
+
+    def episodes_inflight(self):
+        """float64 [N, 6]: {total, agent_0 .. agent_3, length} of every env's running episode."""
+        a = np.empty((self.cfg.n_envs, 6), np.float64)
+        _ck(self.lib.ddrl_episodes_inflight(self.h, a.ctypes.data, a.shape[0]))
+        return a
+
+    def episodes_reset(self):
+        """Forget the in-flight episodes."""
+        _ck(self.lib.ddrl_episodes_reset(self.h))
 
     # ---- learner ----
     def ppo_update(self, mask, shuffles, perms, kl_coeffs, max_steps=-1, step0=0):

@@ -20,6 +20,8 @@ PPO_DEFAULTS = {
     # RLlib-side per-policy filter: exp-1 in the fork uses NoFilter (train_experiment_1:128);
     # the published runs and the shared-policy script use MeanStdFilter (P_Local:139)
     "observation_filter": "NoFilter",
+    # episodes in the window of episode_reward_mean & co. (tests/golden/ppo_params_local.json)
+    "metrics_smoothing_episodes": 100,
 }
 ENV_DEFAULTS = {"ctrl_cost_weight": 0.5, "contact_cost_weight": 5e-2, "hf_smoothness": 1.0,
                 "norm_reward": False, "global_reward": False, "filter_clip": 10.0,

@@ -19,6 +19,7 @@ import time
 import numpy as np
 
 from . import native as N
+from .metrics import EpisodeHistory, ProgressLogger, gather_rank_rows
 from .spec import PPO_DEFAULTS, make_cfg
 
 
@@ -117,6 +118,11 @@ class PPOTrainer:
         if self.parallel not in ("ddp", "replicas", "gather"):
             raise ValueError(f"parallel {self.parallel!r}: 'ddp', 'replicas' or 'gather'")
         self.rctx = self.ctx   # the rollout context (the learner's own, except in "gather" mode)
+        self.episode_history = EpisodeHistory(int(c["metrics_smoothing_episodes"]))
+        self.episodes_total = 0
+        if self.parallel == "replicas" and self.world > 1:   # only the episode metrics cross the ranks
+            from .ddp import Comm
+            self.comm = Comm(self.device if dist.get_backend() == "nccl" else "cpu")
         if self.parallel == "gather":
             from .ddp import Comm
             self.comm = Comm(self.device if self.world > 1 and dist.get_backend() == "nccl" else "cpu") \
@@ -180,6 +186,7 @@ class PPOTrainer:
             rctx.observe(obs)
         rctx.bootstrap()
         rctx.gae()
+        self._episode_rows = self._collect_episodes()
         if self.parallel == "gather":
             from .ddp import sync_filters, sync_standardize, standardize_constants
             for p in range(self.cfg.n_policies):
@@ -213,6 +220,16 @@ class PPOTrainer:
                 self.ctx.policy_filter_delta_reset()
             for p in range(self.cfg.n_policies):
                 self.ctx.adv_norm_set(p, *sync_standardize(self.comm, self.ctx.adv_sums_get(p)))
+
+    def _collect_episodes(self):
+        """The episodes that finished in this fragment, [n, 8] rows in (t, env) order.  Across
+        ranks: counts and padded rows are all-gathered and merged with the global env index
+        rank * n_envs + env, so every rank reports the numbers of one process over all envs."""
+        rows = self.rctx.episodes_collect()
+        comm = getattr(self, "comm", None)
+        if self.world == 1 or comm is None:
+            return rows
+        return gather_rank_rows(comm, rows, self.n_envs)
 
     def _schedule(self, p):
         """SampleBatch.shuffle() + one permutation of the minibatch slots per epoch."""
@@ -288,11 +305,17 @@ class PPOTrainer:
         cb = self.config.get("callbacks", {}).get("on_train_result") if isinstance(
             self.config.get("callbacks"), dict) else None
         self.last_learner = learner
-        result = {"training_iteration": self.iteration, "timesteps_total": self.timesteps_total,
-                  "timesteps_this_iter": steps, "info": {"learner": learner},
-                  "timers": {"sample_time_ms": (t1 - t0) * 1e3, "learn_time_ms": (t2 - t1) * 1e3,
-                             "sample_throughput": steps / (t1 - t0),
-                             "learn_throughput": steps / (t2 - t1)}}
+        # RLlib's result: the episode summary first (summarize_episodes' key order), then the
+        # trainer's own keys -- Tune's progress.csv columns 0-6 follow from this order
+        result = self.episode_history.summarize(self._episode_rows, list(self.cfg.agent_policy)[:self.cfg.n_agents],
+                                                self.policy_ids)
+        self.episodes_total += result["episodes_this_iter"]
+        result.update({"num_healthy_workers": self.world, "timesteps_total": self.timesteps_total,
+                       "timers": {"sample_time_ms": (t1 - t0) * 1e3, "learn_time_ms": (t2 - t1) * 1e3,
+                                  "sample_throughput": steps / (t1 - t0),
+                                  "learn_throughput": steps / (t2 - t1)},
+                       "info": {"learner": learner}, "done": False, "episodes_total": self.episodes_total,
+                       "training_iteration": self.iteration, "timesteps_this_iter": steps})
         if cb:
             cb({"result": result, "trainer": self})
         return result
@@ -689,17 +712,26 @@ def update_kl(kl_coeff, sampled_kl, kl_target=0.01):
     return kl_coeff
 
 
-def run(config, stop=None, n_envs=None, device=0, verbose=True):
-    """tune.run("PPO", config=config, stop={"timesteps_total": ...}) for one trial."""
+def run(config, stop=None, n_envs=None, device=0, verbose=True, logdir=None):
+    """tune.run("PPO", config=config, stop={"timesteps_total": ...}) for one trial.  stop may name
+    any key of the result, e.g. {"episode_reward_mean": 500} (a nan mean -- no episode yet --
+    never stops).  logdir: write Tune's progress.csv and result.json there (ProgressLogger)."""
     stop = stop or {"training_iteration": 1}
     tr = PPOTrainer(config, n_envs=n_envs, device=device)
+    log = ProgressLogger(logdir) if logdir is not None else None
     results = []
-    while True:
-        r = tr.train()
-        results.append(r)
-        if verbose:
-            print(json.dumps({k: r[k] for k in ("training_iteration", "timesteps_total", "timers")}))
-        if any(r.get(k, 0) >= v for k, v in stop.items()):
-            break
+    try:
+        while True:
+            r = tr.train()
+            results.append(r)
+            if log:
+                log.on_result(r)
+            if verbose:
+                print(json.dumps({k: r[k] for k in ("training_iteration", "timesteps_total", "timers")}))
+            if any(r.get(k, 0) >= v for k, v in stop.items()):
+                break
+    finally:
+        if log:
+            log.close()
     tr.stop()
     return results

@@ -288,6 +288,35 @@ int ddrl_gae(ddrl_ctx* ctx);
  * StandardizeFields (the global {mean, max(1e-4, std)} goes back through adv_norm_set). */
 int ddrl_adv_sums_get(ddrl_ctx* ctx, int pid, double* host3);
 
+/* Episode accounting of the training rollout: the episodes that finished in the fragment, as
+ * RLlib 1.0 counts them (3p evaluation/episode.py MultiAgentEpisode._add_agent_rewards, summarized
+ * by 3p evaluation/metrics.py summarize_episodes into episode_reward_mean / episode_len_mean /
+ * policy_reward_mean -- column 2 against column 6 of Tune's progress.csv is every learning curve
+ * of the reference: visualization/visualize_learning_over_time.py:49-53,
+ * stats/compare_learning_performance_atEnd.py:104-108).  Per env step, for every agent in agent
+ * order, agent_total[j] += r and total += r in fp64, r the fp32 reward of the agent's record
+ * (what the learner trains on); length counts env steps and the step that raises done belongs to
+ * the episode it ends.  Only done flags end an episode: an env reset behind the rollout
+ * (update_environment_after_epoch, quantruped_adaptor_multi_environment.py:97-122) does not.
+ * The running sums of every env persist in the context across fragments (allocated by the first
+ * call here).  Deterministic: row positions come from counts and a scan, no atomics.  Writes no
+ * record, done flag, bootstrap value, filter, Adam state or parameter.
+ *   episodes_collect: after the fragment's last ddrl_reward: counts, scans, sizes the table, walks
+ *     the fragment forward.  Synchronizes once.  A fragment is collected at most once (the walk
+ *     advances the in-flight state): a second collect fails until ddrl_reward / ddrl_reward_range,
+ *     ddrl_rollout_hostenv, a ddrl_rollout_fragment launch or ddrl_records_set brought new rewards;
+ *   episodes_rows: the rows of the last collect, n_rows == n_finished, 8 doubles each
+ *     {t, env, length, total, agent_0 .. agent_3} (agents the env does not have: NaN), in
+ *     ascending (t, env) order;
+ *   episodes_inflight: the state of every env's running episode [n_envs][6] =
+ *     {total, agent_0 .. agent_3 (0 for agents the env does not have), length} (tests, diagnostics);
+ *   episodes_reset: forget the in-flight episodes (a caller that resets envs and wants them
+ *     dropped). */
+int ddrl_episodes_collect(ddrl_ctx* ctx, int64_t* n_finished);
+int ddrl_episodes_rows(ddrl_ctx* ctx, double* host, size_t n_rows);
+int ddrl_episodes_inflight(ddrl_ctx* ctx, double* host, size_t n_envs);
+int ddrl_episodes_reset(ddrl_ctx* ctx);
+
 /* PPO update of policy pid_mask bits (a13-a17).  Per policy p (bit p set):
  *   shuffle_dev[p] : int32[R_p] row permutation (SampleBatch.shuffle)
  *   perm_dev[p]    : int32[num_sgd_iter][nb_p] minibatch-slot permutation per epoch,
