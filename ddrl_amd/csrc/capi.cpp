@@ -39,7 +39,6 @@ int fail(const std::string& msg) {
 #define CHK_CTX(c) \
   if (!(c)) return fail("null context")
 
-int ffn_param_count(int d, int A) { return d * 64 * 2 + 128 + 2 * 4096 + 128 + 64 * 2 * A + 2 * A + 65; }
 int gnn_param_count(int A, int layer) { return gnn_param_total(A, layer); }
 
 struct Policy {
@@ -654,6 +653,31 @@ int ddrl_adv_sums_get(ddrl_ctx* c, int pid, double* host3) {
   return 0;
 }
 
+// "cup" model: the leg-coupling table [4][A] follows the policy's fcnet variables (null: none)
+static const float* cup_table(const ddrl_ctx* c, int p) {
+  return c->cfg.leg_coupling ? c->pol[p].theta + ffn_param_count(c->pol[p].d, c->cfg.act_dim) : nullptr;
+}
+
+// the clip of the env-side filter as the kernels take it (0: none)
+static float effective_clip(const ddrl_cfg& g) { return g.filter_enabled ? g.filter_clip : 0.f; }
+
+// stream-ordered copy of a host env plane's pinned buffer
+static int h2d(ddrl_ctx* c, void* dst, const void* src, size_t bytes) {
+  return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : fail("H2D copy failed");
+}
+
+// what ddrl_eval_act and ddrl_eval_sens read of the context
+static PolicyInputArgs make_policy_input(const ddrl_ctx* c, const float* obs) {
+  PolicyInputArgs in{};
+  for (int p = 0; p < c->cfg.n_policies; ++p) {
+    in.theta[p] = c->pol[p].theta;
+    in.cup[p] = cup_table(c, p);
+  }
+  in.obs = obs; in.normc = c->f_normc; in.pf = c->cfg.policy_filter ? c->pf : nullptr;
+  in.clip = effective_clip(c->cfg);
+  return in;
+}
+
 static int check_range(const ddrl_ctx* c, int e0, int e1) {
   if (e0 < 0 || e1 > c->cfg.n_envs || e0 >= e1) return fail("env range [e0, e1) must lie in [0, n_envs) and be non-empty");
   return 0;
@@ -675,13 +699,13 @@ int ddrl_observe_range(ddrl_ctx* c, const float* obs, int e0, int e1) {
   c->sens_act_ok = 0;
   launch_filter_push(c->stream, obs_r, n, g.obs_full_dim, c->f_n, c->f_M, c->f_S, c->f_normc,
                      g.filter_update, g.filter_enabled, c->f_dn, c->f_dM, c->f_dS, c->f_part);
-  const float clip = g.filter_enabled ? g.filter_clip : 0.f;
+  const float clip = effective_clip(g);
   if (g.policy_filter) launch_policy_filter(c->stream, ra, obs_r, c->f_normc, clip, c->zs, c->pf, 1);
   const FilterCount fc{c->f_n, c->f_dn, g.filter_enabled && g.filter_update ? n : 0};
   if (g.model_kind == DDRL_MODEL_FFN)
     launch_observe_ffn(c->stream, ra, obs, c->f_normc, clip, c->stage_tab, g.policy_filter ? c->pf : nullptr, fc);
   else
-    launch_observe_gnn(c->stream, ra, obs, c->f_normc, g.filter_enabled ? g.filter_clip : 0.f, c->pol[0].stage, fc);
+    launch_observe_gnn(c->stream, ra, obs, c->f_normc, clip, c->pol[0].stage, fc);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -697,7 +721,7 @@ static ActArgs make_act(ddrl_ctx* c, int t, const float* eps, float* actions, in
     Policy& P = c->pol[p];
     aa.theta[p] = P.theta; aa.stage[p] = P.stage; aa.rec[p] = P.rec; aa.last_v[p] = P.last_v;
     aa.lay[p] = P.lay; aa.C[p] = P.C;
-    aa.cup[p] = c->cfg.leg_coupling ? P.theta + ffn_param_count(P.d, c->cfg.act_dim) : nullptr;
+    aa.cup[p] = cup_table(c, p);
   }
   aa.t = t; aa.eps = eps; aa.actions = actions; aa.bootstrap = mode;
   aa.e0 = 0; aa.e1 = c->cfg.n_envs;
@@ -898,9 +922,6 @@ int ddrl_rollout_hostenv(ddrl_ctx* c, ddrl_hostenv* env, int groups, const float
   std::vector<hipEvent_t> ev(groups, nullptr);
   for (auto& e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   int rc = 0;
-  auto h2d = [&](void* dst, const void* src, size_t bytes) {
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : fail("H2D copy failed");
-  };
   auto d2h_act = [&](int k) {
     const size_t off = (size_t)lo[k] * 8;
     if (hipMemcpyAsync(env->act + off, c->h_act + off, (size_t)(lo[k + 1] - lo[k]) * 8 * 4, hipMemcpyDeviceToHost,
@@ -911,7 +932,7 @@ int ddrl_rollout_hostenv(ddrl_ctx* c, ddrl_hostenv* env, int groups, const float
   if (reset) env->reset_all();
   for (int k = 0; k < groups && !rc; ++k) {
     const int e0 = lo[k], e1 = lo[k + 1];
-    if (reset) rc = h2d(c->h_obs + (size_t)e0 * D, env->obs + (size_t)e0 * D, (size_t)(e1 - e0) * D * 4) ||
+    if (reset) rc = h2d(c, c->h_obs + (size_t)e0 * D, env->obs + (size_t)e0 * D, (size_t)(e1 - e0) * D * 4) ||
                     ddrl_observe_range(c, c->h_obs, e0, e1);
     rc = rc || ddrl_act_range(c, 0, e0, e1, eps_dev, c->h_act) || d2h_act(k);
   }
@@ -920,10 +941,10 @@ int ddrl_rollout_hostenv(ddrl_ctx* c, ddrl_hostenv* env, int groups, const float
       const int e0 = lo[k], e1 = lo[k + 1], n = e1 - e0;
       if (hipEventSynchronize(ev[k]) != hipSuccess) { rc = fail("event wait failed"); break; }
       env->step(e0, e1);   // host threads; the device meanwhile runs the other groups' work
-      rc = h2d(c->h_fw + e0, env->fw + e0, (size_t)n * 4) ||
-           h2d(c->h_cfrc + (size_t)e0 * 84, env->cfrc + (size_t)e0 * 84, (size_t)n * 84 * 4) ||
-           h2d(c->h_done + e0, env->done + e0, (size_t)n) ||
-           h2d(c->h_obs + (size_t)e0 * D, env->obs + (size_t)e0 * D, (size_t)n * D * 4) ||
+      rc = h2d(c, c->h_fw + e0, env->fw + e0, (size_t)n * 4) ||
+           h2d(c, c->h_cfrc + (size_t)e0 * 84, env->cfrc + (size_t)e0 * 84, (size_t)n * 84 * 4) ||
+           h2d(c, c->h_done + e0, env->done + e0, (size_t)n) ||
+           h2d(c, c->h_obs + (size_t)e0 * D, env->obs + (size_t)e0 * D, (size_t)n * D * 4) ||
            ddrl_reward_range(c, t, e0, e1, c->h_fw, c->h_cfrc, c->h_act, c->h_done) ||
            ddrl_observe_range(c, c->h_obs, e0, e1);
       if (!rc && t + 1 < T)
@@ -984,7 +1005,7 @@ int ddrl_eval_act(ddrl_ctx* c, const float* obs, const float* eps, float* action
   const ddrl_cfg& g = c->cfg;
   const int N = g.n_envs;
   const int push = g.filter_enabled && c->ev_cfg.filter_update;
-  const float clip = g.filter_enabled ? g.filter_clip : 0.f;
+  const float clip = effective_clip(g);
   // the normalization constants are rewritten only when a push changes them, or when this is
   // the first step since something else (eval_begin, filter_set, observe) may have
   if (push || !c->ev_normc_ok) {
@@ -995,13 +1016,8 @@ int ddrl_eval_act(ddrl_ctx* c, const float* obs, const float* eps, float* action
     c->ev_normc_ok = !push;
   }
   EvalActArgs ea{};
-  for (int p = 0; p < g.n_policies; ++p) {
-    const Policy& P = c->pol[p];
-    ea.theta[p] = P.theta;
-    ea.cup[p] = g.leg_coupling ? P.theta + ffn_param_count(P.d, g.act_dim) : nullptr;
-    ea.logits_out[p] = logits_out ? logits_out[p] : nullptr;
-  }
-  ea.obs = obs; ea.normc = c->f_normc; ea.pf = g.policy_filter ? c->pf : nullptr; ea.clip = clip;
+  ea.in = make_policy_input(c, obs);
+  for (int p = 0; p < g.n_policies; ++p) ea.logits_out[p] = logits_out ? logits_out[p] : nullptr;
   ea.eps = eps; ea.actions = actions;
   ea.fc = FilterCount{c->f_n, c->f_dn, push ? N : 0};
   RouteArgs ra = c->route;
@@ -1106,16 +1122,12 @@ int ddrl_eval_sens(ddrl_ctx* c, const float* obs, float* const* means_out) {
     return fail("sensitivity: call ddrl_eval_act on this observation first (the filter constants may have changed)");
   const ddrl_cfg& g = c->cfg;
   EvalSensArgs sa{};
+  sa.in = make_policy_input(c, obs);
   for (int p = 0; p < g.n_policies; ++p) {
-    const Policy& P = c->pol[p];
-    sa.theta[p] = P.theta;
-    sa.cup[p] = g.leg_coupling ? P.theta + ffn_param_count(P.d, g.act_dim) : nullptr;
     sa.means_out[p] = means_out ? means_out[p] : nullptr;
     sa.acc[p] = c->sens_acc[p];
     sa.rowcnt[p] = c->sens_cnt[p];
   }
-  sa.obs = obs; sa.normc = c->f_normc; sa.pf = g.policy_filter ? c->pf : nullptr;
-  sa.clip = g.filter_enabled ? g.filter_clip : 0.f;
   sa.step = c->sens_step; sa.ep_count = c->ev_count; sa.E = c->ev_cfg.episodes_per_env;
   // one base row per workgroup up to 512 rows per policy, a loop over base rows past that (the
   // measured choice, DESIGN.md "Sensitivity"); DDRL_SENS_GRID (read at every launch) moves the cap
@@ -1157,11 +1169,8 @@ int ddrl_eval_hostenv(ddrl_ctx* c, ddrl_hostenv* env, const float* eps_dev, int 
   const size_t N = g.n_envs, D = g.obs_full_dim;
   const size_t eps_step = N * g.n_agents * g.act_dim;
   const int limit = eps_dev ? std::min(max_steps, eps_steps) : max_steps;
-  auto h2d = [&](void* dst, const void* src, size_t bytes) {
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : fail("H2D copy failed");
-  };
   env->reset_episodes();
-  int rc = h2d(c->h_obs, env->obs, N * D * 4);
+  int rc = h2d(c, c->h_obs, env->obs, N * D * 4);
   int t = 0;
   for (; t < limit && !rc;) {
     rc = ddrl_eval_act(c, c->h_obs, eps_dev ? eps_dev + (size_t)t * eps_step : nullptr, c->h_act, nullptr);
@@ -1172,8 +1181,8 @@ int ddrl_eval_hostenv(ddrl_ctx* c, ddrl_hostenv* env, const float* eps_dev, int 
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail("stream synchronize failed");
     if (rc) break;
     env->step(0, (int)N);
-    rc = h2d(c->h_fw, env->fw, N * 4) || h2d(c->h_cfrc, env->cfrc, N * 84 * 4) || h2d(c->h_done, env->done, N) ||
-         h2d(c->ev_kin, env->kin, N * 9 * 4) || h2d(c->h_obs, env->obs, N * D * 4) ||
+    rc = h2d(c, c->h_fw, env->fw, N * 4) || h2d(c, c->h_cfrc, env->cfrc, N * 84 * 4) || h2d(c, c->h_done, env->done, N) ||
+         h2d(c, c->ev_kin, env->kin, N * 9 * 4) || h2d(c, c->h_obs, env->obs, N * D * 4) ||
          ddrl_eval_step(c, c->h_fw, c->h_cfrc, c->h_act, c->ev_kin, c->h_done);
     ++t;
     if (!rc && t % poll_every == 0) {
@@ -1697,7 +1706,7 @@ int ddrl_policy_forward(ddrl_ctx* c, int pid, const float* obs, const int32_t* n
   ForwardArgs fa{};
   fa.theta = P.theta; fa.x = obs; fa.node = node; fa.n = n; fa.d = P.d; fa.A = c->cfg.act_dim;
   fa.logits = logits; fa.values = values;
-  fa.cup = c->cfg.leg_coupling ? P.theta + ffn_param_count(P.d, c->cfg.act_dim) : nullptr;
+  fa.cup = cup_table(c, pid);
   if (c->cfg.model_kind == DDRL_MODEL_FFN) launch_forward_ffn(c->stream, fa);
   else launch_forward_gnn(c->stream, fa, c->cfg.gnn_layer);
   HIPCHK(hipGetLastError());

@@ -54,6 +54,29 @@ __device__ inline void stage_weights(const float* __restrict__ th, int d, int A,
 }
 #define LDS_WEIGHTS_FLOATS(O) (2 * LDS_W1 + 2 * LDS_W2 + 4 * 64 + 64 * (O) + (O) + 64 + 1)
 
+// The policy branch's half of that image, for the kernels that never run the value branch
+// (evaluation, sensitivity): the same swizzled w1 / w2 and the same b1 / b2 / wo / bo.
+#define LDS_POLICY_FLOATS(O) (LDS_W1 + LDS_W2 + 2 * 64 + 64 * (O) + (O))
+__device__ __forceinline__ void stage_policy_weights(const float* __restrict__ th, int d, int A, float* lds,
+                                                     NetLds& P, int nthreads) {
+  const FfnOffsets o = ffn_offsets(d, A);
+  const int O = 2 * A;
+  P.w1 = lds;         P.w2 = P.w1 + LDS_W1;
+  P.b1 = P.w2 + LDS_W2;  P.b2 = P.b1 + 64;
+  P.wo = P.b2 + 64;   P.bo = P.wo + 64 * O;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < 48 * 64; i += nthreads) {
+    const int f = i >> 6, col = i & 63;
+    P.w1[sidx(f, col)] = f < d ? th[o.w1 + i] : 0.f;
+  }
+  for (int i = tid; i < 64 * 64; i += nthreads) P.w2[sidx(i >> 6, i & 63)] = th[o.w2 + i];
+  for (int i = tid; i < 64; i += nthreads) {
+    P.b1[i] = th[o.b1 + i];
+    P.b2[i] = th[o.b2 + i];
+  }
+  for (int i = tid; i < 64 * O; i += nthreads) P.wo[i] = th[o.wo + i];
+  for (int i = tid; i < O; i += nthreads) P.bo[i] = th[o.bo + i];
+}
 
 // Compile-time (A, ceil(d/4)) instantiation for the observation widths of the reference's
 // envs: d = 19/20 (FullyDecentral, Shared), 27/28 (SingleNeighbor/Diagonal/ToFront,

@@ -36,6 +36,18 @@ struct RouteArgs {
   float leg_angle[4];
 };
 
+// launch geometry of the per-row kernels: the most rows (n_envs * k) and the widest observation
+// of the routed policies
+struct RowGeom { int rows, d; };
+inline RowGeom row_geom(const RouteArgs& ra, int n_envs) {
+  RowGeom g{0, 0};
+  for (int p = 0; p < ra.P; ++p) {
+    g.rows = ra.pol[p].k * n_envs > g.rows ? ra.pol[p].k * n_envs : g.rows;
+    g.d = ra.pol[p].d > g.d ? ra.pol[p].d : g.d;
+  }
+  return g;
+}
+
 // ---- filter / observe (rollout.hip) ----
 // dn / dM / dS: a second running stat of the pushes since the last cross-rank filter sync
 // part: filter_part_doubles(N, D) doubles of per-chunk (mean, M2) scratch
@@ -102,14 +114,18 @@ void launch_reward(hipStream_t s, const RewardArgs& ra, const float* fw, const f
                    const float* actions, const uint8_t* done, uint8_t* done_tn);
 
 // ---- evaluation (eval.hip): fused observe + forward + action, episode statistics ----
-struct EvalActArgs {
+// what the evaluation kernels read to turn a raw observation into a policy's action means
+struct PolicyInputArgs {
   const float* theta[DDRL_MAXP];
   const float* cup[DDRL_MAXP];     // "cup" leg-coupling table [4][A] (nullptr: none)
-  float* logits_out[DDRL_MAXP];    // optional [C_p][2A] logits of this step (nullptr: not written)
   const float* obs;                // raw observations [N][full_dim]
   const double* normc;             // env-side filter constants (mean, std + 1e-8) per column
   const double* pf;                // per-policy filter state (PF_* layout) or nullptr
   float clip;
+};
+struct EvalActArgs {
+  PolicyInputArgs in;
+  float* logits_out[DDRL_MAXP];    // optional [C_p][2A] logits of this step (nullptr: not written)
   const float* eps;                // [N][n_agents][A]; nullptr: deterministic (the mean)
   float* actions;                  // [N][8]
   FilterCount fc;                  // batch count of this step's env-side filter push (0: none)
@@ -129,15 +145,10 @@ void launch_eval_accum(hipStream_t s, const RewardArgs& ra, const EvalAccumArgs&
 
 // ---- input sensitivity of the evaluated policies (eval_sens.hip) ----
 struct EvalSensArgs {
-  const float* theta[DDRL_MAXP];
-  const float* cup[DDRL_MAXP];     // "cup" leg-coupling table [4][A] (nullptr: none)
+  PolicyInputArgs in;              // normc: as the step's ddrl_eval_act read them
   float* means_out[DDRL_MAXP];     // optional [C_p][2 d][A] clipped means of the perturbed rows (nullptr)
   double* acc[DDRL_MAXP];          // [C_p][2][d][A]: per base row, sum of (plus - minus) and of its magnitude
   long long* rowcnt[DDRL_MAXP];    // [C_p] steps accumulated per base row
-  const float* obs;                // raw observations [N][full_dim]
-  const double* normc;             // env-side filter constants, as the step's ddrl_eval_act read them
-  const double* pf;                // per-policy filter state (PF_* layout) or nullptr
-  float clip;
   const double* step;              // [P][DDRL_MAXD] perturbation h_f of the env-normalized input
   const int32_t* ep_count;         // [N] episodes recorded per env (the quota gate)
   int E;
@@ -242,6 +253,7 @@ struct ForwardArgs {
   float* logits; float* values;
 };
 void launch_forward_ffn(hipStream_t s, const ForwardArgs& fa);
+int ffn_param_count(int d, int A);       // fcnet variables of one policy (ffn.h ffn_offsets)
 void launch_forward_gnn(hipStream_t s, const ForwardArgs& fa, int layer);
 
 // ---- GraphNet (gnn.hip): per-tile kernels, one minibatch step = grad / reduce / Adam ----

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "ffn.h"
+#include "policy_io.h"
 
 // ------------------------------------------------------------------------------------
 // a2: batched MeanStdFilter push, two launches.  k_filter_chunk: workgroup (j, s) reduces rows
@@ -93,27 +94,6 @@ void launch_filter_push(hipStream_t s, const float* obs, int N, int D, double* n
                      dn, dM, dS);
 }
 
-// The running count of the env-side filter advances after every column of k_filter_push has
-// read it: the observe kernel that follows adds the batch (FilterCount: count = N, or 0 when
-// the filter did not push).
-__device__ __forceinline__ void filter_count(const FilterCount& fc) {
-  if (fc.count && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-    fc.n_run[0] += (double)fc.count;
-    fc.dn[0] += (double)fc.count;
-  }
-}
-
-__device__ __forceinline__ double norm_obs_d(float x, const double* normc, int idx, float clip) {
-  double z = ((double)x - normc[2 * idx]) / normc[2 * idx + 1];
-  if (clip > 0.f) z = fmin(fmax(z, -(double)clip), (double)clip);
-  return z;
-}
-__device__ __forceinline__ float norm_obs(float x, const double* normc, int idx, float clip) {
-  double z = ((double)x - normc[2 * idx]) / normc[2 * idx + 1];
-  if (clip > 0.f) z = fmin(fmax(z, -(double)clip), (double)clip);
-  return (float)z;
-}
-
 // a1: per-agent gather of the normalized observation into stage[p][c][f].
 __global__ void k_observe_ffn(RouteArgs ra, const float* __restrict__ obs,
                               const double* __restrict__ normc, float clip, float* const* stage_tab,
@@ -127,17 +107,8 @@ __global__ void k_observe_ffn(RouteArgs ra, const float* __restrict__ obs,
   const int cl = gid / pr.d, f = gid - cl * pr.d;
   const int el = cl / pr.k, slot = cl - el * pr.k;
   const int e = ra.e0 + el, c = ra.e0 * pr.k + cl;
-  const int idx = pr.obs_index[slot][f];
-  float v;
-  if (idx < 0) {
-    v = idx == -2 ? 1.f : 0.f;
-  } else if (pf) {   // RLlib MeanStdFilter on the fp64 env-normalized value
-    const double* P = pf + (size_t)p * PF_STRIDE + PF_NORMC;
-    v = (float)((norm_obs_d(obs[(size_t)e * ra.full_dim + idx], normc, idx, clip) - P[2 * f]) / P[2 * f + 1]);
-  } else {
-    v = norm_obs(obs[(size_t)e * ra.full_dim + idx], normc, idx, clip);
-  }
-  stage_tab[p][(size_t)c * pr.d + f] = v;
+  stage_tab[p][(size_t)c * pr.d + f] =
+      routed_input(pr, slot, f, obs + (size_t)e * ra.full_dim, normc, clip, policy_filter_normc(pf, p));
 }
 
 void launch_observe_ffn(hipStream_t s, const RouteArgs& ra, const float* obs, const double* normc,
@@ -333,8 +304,7 @@ __global__ void __launch_bounds__(512) k_act_ffn(RouteArgs ra, ActArgs aa) {
 #pragma unroll
     for (int j = 0; j < A; ++j) {
       rp[L.act + j] = act[j];
-      const float ac = fminf(fmaxf(act[j], -1.f), 1.f);
-      aa.actions[(size_t)e * 8 + pr.act_index[slot][j]] = (pr.act_neg[slot] >> j) & 1 ? -ac : ac;
+      scatter_action(aa.actions, pr, e, slot, j, act[j]);
     }
   } else if (q == 1) {
 #pragma unroll
@@ -351,12 +321,9 @@ static void launch_act_t(hipStream_t s, dim3 grid, const RouteArgs& ra, const Ac
 }
 
 void launch_act_ffn(hipStream_t s, const RouteArgs& ra, const ActArgs& aa) {
-  int maxC = 0;
-  for (int p = 0; p < ra.P; ++p) maxC = max(maxC, (aa.e1 - aa.e0) * ra.pol[p].k);
-  dim3 grid((maxC + 63) / 64, ra.P);
-  int maxd = 0;
-  for (int p = 0; p < ra.P; ++p) maxd = max(maxd, ra.pol[p].d);
-  DDRL_DISPATCH_A_KS1(ra.A, maxd, launch_act_t, s, grid, ra, aa);
+  const RowGeom g = row_geom(ra, aa.e1 - aa.e0);
+  dim3 grid((g.rows + 63) / 64, ra.P);
+  DDRL_DISPATCH_A_KS1(ra.A, g.d, launch_act_t, s, grid, ra, aa);
 }
 
 // ------------------------------------------------------------------------------------
@@ -370,38 +337,7 @@ __global__ void k_reward(RewardArgs ra, const float* __restrict__ fw, const floa
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= ra.n * na) return;
   const int el = gid / na, j = gid - el * na, e = ra.e0 + el;
-  const float* cf = cfrc + (size_t)e * 14 * 6;
-  const float* a8 = actions + (size_t)e * 8;
-  const double fwd = fw[e];
-  double r;
-  if (ra.mode == 1) {
-    double ctrl_all = 0.0, contact_all = 0.0;
-    for (int i = 0; i < 8; ++i) ctrl_all += (double)a8[i] * a8[i];
-    for (int i = 0; i < 14 * 6; ++i) {
-      const double v = fmin(fmax((double)cf[i], -1.0), 1.0);
-      contact_all += v * v;
-    }
-    contact_all *= ra.contact_w;
-    r = (fwd - ra.ctrl_w * ctrl_all - contact_all) / na;
-  } else {
-    double ctrl = 0.0;
-    for (int i = 0; i < ra.n_act[j]; ++i) {
-      const double a = a8[ra.act_index[j][i]];
-      ctrl += a * a;
-    }
-    double contact = 0.0;
-    for (int b = 0; b < ra.n_contact[j]; ++b) {
-      const float* body = cf + ra.contact_index[j][b] * 6;
-      double sb = 0.0;
-      for (int k = 0; k < 6; ++k) {
-        const double v = fmin(fmax((double)body[k], -1.0), 1.0);
-        sb += ra.contact_w * v * v * ra.contact_weight[j][b];
-      }
-      contact += sb;
-    }
-    r = ra.mode == 2 ? fwd - na * (ra.ctrl_w * ctrl + contact)
-                     : fwd / na - ra.ctrl_w * ctrl - contact;
-  }
+  const double r = agent_reward_d(ra, j, (double)fw[e], cfrc + (size_t)e * 14 * 6, actions + (size_t)e * 8);
   const int p = ra.policy_of_agent[j], slot = ra.slot_of_agent[j];
   const size_t C = (size_t)ra.N * ra.k[p];
   float* rp = ra.rec[p] + ((size_t)ra.t * C + (size_t)e * ra.k[p] + slot) * ra.lay[p].stride;
@@ -415,6 +351,8 @@ void launch_reward(hipStream_t s, const RewardArgs& ra, const float* fw, const f
   hipLaunchKernelGGL(k_reward, dim3((n + 255) / 256), dim3(256), 0, s, ra, fw, cfrc, actions,
                      done, done_tn);
 }
+
+int ffn_param_count(int d, int A) { return ffn_offsets(d, A).n; }
 
 // ------------------------------------------------------------------------------------
 // ModelV2.forward + value_function (fcnet_glorot_uniform_init.py:120-125) on n rows.

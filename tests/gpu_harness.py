@@ -20,6 +20,17 @@ def make_ctx(env, n_envs, T, config=None, stream=None, cfg_set=None):
     return ctx, cfg, inst
 
 
+def dev(a):
+    """A host array as a device tensor."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def filter_state(D, rng):
+    """A seeded env-side filter state (n, M, S) away from the initial one."""
+    return (1000.0, rng.normal(size=D) * 0.3, np.abs(rng.normal(size=D)) * 999.0 + 10.0)
+
+
 def policy_tables(cfg, inst):
     """Per policy: list of (slot -> agent name) and d, from the cfg the kernels use."""
     agents = list(inst.agent_names)
@@ -195,7 +206,6 @@ def run_rollout(ctx, cfg, inst, params, rng, filt, T, orc_cls=None, pfilt=None):
         for p, (n, M, S) in enumerate(pfilt):
             ctx.policy_filter_set(p, n, M, S)
             orc.pf[p].n, orc.pf[p].M[:], orc.pf[p].S[:] = n, M, S
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     actions = torch.zeros((cfg.n_envs, 8), dtype=torch.float32, device="cuda")
     acts_gpu = []
     acts_orc = []
@@ -255,6 +265,11 @@ def init_cup_params(ctx, cfg, seed, head_scale=30.0, perturb=True):
         pr["leg_coupling"] = (pr["leg_coupling"] * rng.uniform(0.5, 1.5, size=(4, A))).astype(np.float32)
     ctx.params_set(0, O.pack(pr, O.cup_param_shapes(d, A)))
     return [pr]
+
+
+def init_policy_params(ctx, cfg, seed, cup):
+    """Unit-head seeded parameters of every policy, with the coupling table when cup."""
+    return init_cup_params(ctx, cfg, seed, head_scale=1.0) if cup else init_params(ctx, cfg, seed, head_scale=1.0)
 
 
 class CupOracleRollout(OracleRollout):

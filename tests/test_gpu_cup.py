@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 from oracle import ddrl_oracle as O
-from tests.gpu_harness import (CUP_CONFIG, CUP_ENV, CupOracleRollout, init_cup_params, make_ctx, run_rollout,
-                                strict_params_check)
+from tests.gpu_harness import (CUP_CONFIG, CUP_ENV, CupOracleRollout, filter_state, init_cup_params, make_ctx,
+                               run_rollout, strict_params_check)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +25,6 @@ def _gpu():
         pytest.skip("no GPU")
     from ddrl_amd import build
     build.build()
-
-
-def _filt(D, rng):
-    return (1000.0, rng.normal(size=D) * 0.3, np.abs(rng.normal(size=D)) * 999.0 + 10.0)
 
 
 def _batch(rec, lay, d, A, adv_norm):
@@ -44,7 +40,7 @@ def _rollout(n, T, seed, head_scale=30.0):
     assert cfg.leg_coupling == 1 and cfg.obs_dim[0] == 19
     rng = np.random.default_rng(seed)
     params = init_cup_params(ctx, cfg, seed + 1, head_scale=head_scale)
-    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T,
+    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T,
                                            orc_cls=CupOracleRollout)
     return ctx, cfg, params, orc, norms, a_gpu, a_orc
 

@@ -13,8 +13,7 @@ import socket
 import numpy as np
 import pytest
 
-from tests.gpu_harness import (GnnOracleRollout, init_gnn_params, init_params, make_ctx,
-                               run_rollout)
+from tests.gpu_harness import GnnOracleRollout, filter_state, init_gnn_params, init_params, make_ctx, run_rollout
 from oracle import ddrl_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -43,20 +42,16 @@ def pg1():
     dist.destroy_process_group()
 
 
-def _filt(D, rng):
-    return (1000.0, rng.normal(size=D) * 0.3, np.abs(rng.normal(size=D)) * 999.0 + 10.0)
-
-
 def _pair(env, n, T, gnn):
     """Context a after a rollout, context b with a's records, advantage norm and weights."""
     ctx, cfg, inst = make_ctx(env, n, T)
     rng = np.random.default_rng(41)
     if gnn:
         params = init_gnn_params(ctx, 42, head_scale=1.0)
-        run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T, orc_cls=GnnOracleRollout)
+        run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T, orc_cls=GnnOracleRollout)
     else:
         params = init_params(ctx, cfg, 42, head_scale=1.0)
-        run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T)
+        run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T)
     ctx_b, _, _ = make_ctx(env, n, T)
     ctx_b.params_set(0, ctx.params_get(0))
     ctx_b.records_set(0, ctx.records_get(0))
@@ -129,7 +124,7 @@ def test_grad_launches_across_epoch_wrap():
     ctx, cfg, inst = make_ctx("QuantrupedMultiEnv_SharedDecentral", 32, 4)
     rng = np.random.default_rng(3)
     params = init_params(ctx, cfg, 5, head_scale=1.0)
-    run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), 4)
+    run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), 4)
     R = ctx.records_get(0).shape[0]
     perm = torch.from_numpy(np.random.default_rng(9).permutation(R).astype(np.int32)).cuda()
     rows = [perm[:128], perm[128:256]]

@@ -13,7 +13,7 @@ import pytest
 
 from ddrl_amd import native as N
 from tests import episodes_reference as R
-from tests.gpu_harness import init_params, make_ctx
+from tests.gpu_harness import dev, init_params, make_ctx
 
 pytestmark = pytest.mark.gpu
 U = 16
@@ -22,19 +22,14 @@ ENVS = {"centralized": "QuantrupedMultiEnv_Centralized", "twosides": "Quantruped
         "local": LOCAL, "shared": "QuantrupedMultiEnv_SharedDecentral"}
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _drive(ctx, cfg, rng, done, steps=None):
     """Rewards of the steps (all by default) through ddrl_reward with the scripted done flags."""
     T, n = done.shape
-    actions = _dev(rng.uniform(-1, 1, size=(n, 8)).astype(np.float32))
+    actions = dev(rng.uniform(-1, 1, size=(n, 8)).astype(np.float32))
     for t in (range(T) if steps is None else steps):
-        fw = _dev(rng.normal(size=n).astype(np.float32))
-        cfrc = _dev((rng.normal(size=(n, 14, 6)) * 1.5).astype(np.float32))
-        ctx.reward(t, fw, cfrc, actions, _dev(done[t]))
+        fw = dev(rng.normal(size=n).astype(np.float32))
+        cfrc = dev((rng.normal(size=(n, 14, 6)) * 1.5).astype(np.float32))
+        ctx.reward(t, fw, cfrc, actions, dev(done[t]))
 
 
 def _collect_and_check(ctx, cfg, ref, done):
@@ -234,12 +229,12 @@ def _rollout(ctx, cfg, rng, T, done):
     import torch
     n = cfg.n_envs
     actions = torch.zeros((n, 8), dtype=torch.float32, device="cuda")
-    ctx.observe(_dev((rng.normal(size=(n, cfg.obs_full_dim)) * 2 + 0.5).astype(np.float32)))
+    ctx.observe(dev((rng.normal(size=(n, cfg.obs_full_dim)) * 2 + 0.5).astype(np.float32)))
     for t in range(T):
-        ctx.act(t, _dev(rng.normal(size=(n, cfg.n_agents, cfg.act_dim)).astype(np.float32)), actions)
-        ctx.reward(t, _dev(rng.normal(size=n).astype(np.float32)),
-                   _dev((rng.normal(size=(n, 14, 6)) * 1.5).astype(np.float32)), actions, _dev(done[t]))
-        ctx.observe(_dev((rng.normal(size=(n, cfg.obs_full_dim)) * 2 + 0.5).astype(np.float32)))
+        ctx.act(t, dev(rng.normal(size=(n, cfg.n_agents, cfg.act_dim)).astype(np.float32)), actions)
+        ctx.reward(t, dev(rng.normal(size=n).astype(np.float32)),
+                   dev((rng.normal(size=(n, 14, 6)) * 1.5).astype(np.float32)), actions, dev(done[t]))
+        ctx.observe(dev((rng.normal(size=(n, cfg.obs_full_dim)) * 2 + 0.5).astype(np.float32)))
     ctx.bootstrap()
 
 
@@ -282,8 +277,8 @@ def test_collect_leaves_training_alone():
     for p in range(P):
         Rr = T * a.layout[p]["C"]
         nb = max(1, Rr // cfg.sgd_minibatch_size)
-        sh.append(_dev(srng.permutation(Rr).astype(np.int32)))
-        pe.append(_dev(np.stack([srng.permutation(nb) for _ in range(cfg.num_sgd_iter)]).astype(np.int32)))
+        sh.append(dev(srng.permutation(Rr).astype(np.int32)))
+        pe.append(dev(np.stack([srng.permutation(nb) for _ in range(cfg.num_sgd_iter)]).astype(np.int32)))
     for ctx in (a, b):
         ctx.ppo_update((1 << P) - 1, sh, pe, [0.2] * P, max_steps=20)
         ctx.synchronize()

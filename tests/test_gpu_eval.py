@@ -14,8 +14,8 @@ from ddrl_amd import native as N
 from ddrl_amd.spec import make_cfg
 from oracle import ddrl_oracle as O
 from tests import eval_reference as R
-from tests.gpu_harness import (CUP_CONFIG, CUP_ENV, GNN_ENV, CupOracleRollout, OracleRollout, init_cup_params,
-                               init_params, run_rollout, synthetic_inputs)
+from tests.gpu_harness import (CUP_CONFIG, CUP_ENV, GNN_ENV, CupOracleRollout, OracleRollout, dev, init_params,
+                               init_policy_params, run_rollout, synthetic_inputs)
 
 pytestmark = pytest.mark.gpu
 PARITY = dict(rtol=1e-5, atol=2e-5)
@@ -28,17 +28,8 @@ def _ctx(env, n, T, config=None, filter_update=1):
     return N.Context(cfg, 0, torch.cuda.current_stream().cuda_stream), cfg, inst
 
 
-def _init(ctx, cfg, seed, cup):
-    return init_cup_params(ctx, cfg, seed, head_scale=1.0) if cup else init_params(ctx, cfg, seed, head_scale=1.0)
-
-
 def _filt(D, rng):
     return 100.0, rng.normal(size=D) * 0.1, np.abs(rng.normal(size=D)) * 99 + 1
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _logit_bufs(ctx, cfg):
@@ -70,9 +61,9 @@ def test_eval_act_parity(env, n, config):
     twin0, _, _ = _ctx(env, n, T, config, filter_update=0)
     twin1, _, _ = _ctx(env, n, T, config, filter_update=1)
     rng = np.random.default_rng(31)
-    params = _init(ectx, cfg, 5, cup)
+    params = init_policy_params(ectx, cfg, 5, cup)
     for c in (twin0, twin1):
-        _init(c, cfg, 5, cup)
+        init_policy_params(c, cfg, 5, cup)
     D, A = cfg.obs_full_dim, cfg.act_dim
     assert D == (44 if "target_velocity" in str(config) else 43)
     filt = _filt(D, rng)
@@ -93,7 +84,7 @@ def test_eval_act_parity(env, n, config):
     ectx.eval_begin(1, filter_update=False)
     inside = total = 0
     for t in range(T):
-        o_t, e_t = _dev(obs[t]), _dev(eps[t])
+        o_t, e_t = dev(obs[t]), dev(eps[t])
         twin0.observe(o_t)
         twin0.act(t, e_t, act_t)
         twin0.synchronize()
@@ -138,7 +129,7 @@ def test_eval_act_parity(env, n, config):
     ectx.eval_begin(1, filter_update=True)
     pbefore = [ectx.policy_filter_get(p) for p in range(cfg.n_policies)]
     for t in range(T):
-        o_t = _dev(obs[t])
+        o_t = dev(obs[t])
         ectx.eval_act(o_t, None, act_d)
         twin1.observe(o_t)
     ectx.synchronize()
@@ -172,7 +163,7 @@ def _run_scripted(ctx, cfg, inst, E, inputs, filter_update=False):
     ref = R.EpisodeAccumulator(n, E)
     ctx.eval_begin(E, filter_update=filter_update)
     for t in range(T):
-        ctx.eval_step(_dev(fw[t]), _dev(cfrc[t]), _dev(actions[t]), _dev(kin[t]), _dev(done[t]))
+        ctx.eval_step(dev(fw[t]), dev(cfrc[t]), dev(actions[t]), dev(kin[t]), dev(done[t]))
         ref.step(R.step_rewards(cfg, inst, fw[t], cfrc[t], actions[t]), actions[t], kin[t], done[t])
     progress = ctx.eval_progress()
     table = ctx.eval_results()
@@ -234,6 +225,50 @@ def _episode_accounting(n, config, n_inputs):
     ctx.close()
 
 
+REWARD_MODES = [pytest.param(None, N.REWARD_PER_LEG, id="per_leg"),
+                pytest.param({"env_config": {"global_reward": True}}, N.REWARD_GLOBAL, id="global"),
+                pytest.param({"env_config": {"norm_reward": True}}, N.REWARD_NORM, id="norm")]
+
+
+@pytest.mark.parametrize("config,mode", REWARD_MODES)
+@pytest.mark.parametrize("env,n", [
+    pytest.param("QuantrupedMultiEnv_Local", 5, id="local5"),       # a ragged last group of four lanes
+    pytest.param("QuantrupedMultiEnv_Local", 65, id="local65"),     # the second 256-thread block
+    pytest.param("QuantrupedMultiEnv_SharedDecentral", 5, id="shared5")])   # k = 4: one policy, four slots
+def test_reward_record_and_episode_return_agree(env, n, config, mode):
+    """The two consumers of the per-agent reward on the same context and inputs: ddrl_reward rounds
+    every agent's fp64 reward to fp32 into its record, ddrl_eval_step sums the same fp64 rewards.
+    With every env done at its first step the table's return is that sum, so it differs from the
+    fp64 sum of the env's record fields r_j by the records' roundings alone: at most
+    sum_j |r_j| 2^-24 (half an ulp each), with 1e-9 of slack for the fp64 additions."""
+    ctx, cfg, inst = _ctx(env, n, 1, config)
+    assert cfg.reward_mode == mode
+    fw, cfrc, actions, kin, _ = _scripted(cfg, 1, n)
+    f_d, c_d, a_d = dev(fw[0]), dev(cfrc[0]), dev(actions[0])
+    ctx.reward(0, f_d, c_d, a_d)
+    ctx.eval_begin(1)
+    ctx.eval_step(f_d, c_d, a_d, dev(kin[0]), dev(np.ones(n, np.uint8)))
+    ret = ctx.eval_results()[:, 0, 0]
+    ctx.eval_end()
+    r = np.zeros((n, cfg.n_agents))   # the fp32 record fields, exact in fp64
+    for p in range(cfg.n_policies):
+        agents = [j for j in range(cfg.n_agents) if cfg.agent_policy[j] == p]
+        lay = ctx.layout[p]
+        rew = ctx.records_get(p)[:lay["C"], lay["rew"]].reshape(n, len(agents))
+        assert rew.dtype == np.float32
+        for slot, j in enumerate(agents):
+            r[:, j] = rew[:, slot]
+    ctx.close()
+    assert np.isfinite(ret).all() and (r != 0).all()
+    total = np.zeros(n)
+    for j in range(cfg.n_agents):   # agent order, as the accumulator adds
+        total += r[:, j]
+    err, bound = np.abs(ret - total), np.abs(r).sum(1) * 2.0 ** -24 * (1 + 1e-9)
+    print(f"max |return - sum of records| = {err.max():.3e}, largest share of its bound = {(err / bound).max():.3f}")
+    assert (err <= bound).all(), (err / bound).max()
+    assert (err > 0).any()   # the return is not the sum of the rounded records
+
+
 def test_zero_distance_episode_gives_ieee_results():
     ctx, cfg, inst = _ctx("QuantrupedMultiEnv_Local", 3, 2)
     z = lambda *s: np.zeros(s, np.float32)
@@ -243,7 +278,7 @@ def test_zero_distance_episode_gives_ieee_results():
     act = z(3, 8)
     act[:2] = 0.5         # env 2: no power either -> 0 / 0
     ctx.eval_begin(1)
-    ctx.eval_step(_dev(z(3)), _dev(z(3, 14, 6)), _dev(act), _dev(kin), _dev(np.ones(3, np.uint8)))
+    ctx.eval_step(dev(z(3)), dev(z(3, 14, 6)), dev(act), dev(kin), dev(np.ones(3, np.uint8)))
     t = ctx.eval_results()[:, 0]
     assert t[0, 2] == 0 and t[0, 4] == 0 and np.isposinf(t[0, 5])          # distance 0: velocity 0, CoT inf
     assert t[1, 4] == 0.5 and t[1, 5] == (4.0 / 1) / (N.TOTAL_MASS * 0.5)  # 8 joints x |0.5 * 1|
@@ -285,8 +320,8 @@ def test_evaluation_leaves_the_training_state_alone():
     actions = torch.zeros((n, 8), dtype=torch.float32, device="cuda")
     ctx.eval_begin(2, filter_update=False)
     for t in range(12):
-        ctx.eval_act(_dev(obs[t]), _dev(eps[t]) if t % 2 else None, actions)
-        ctx.eval_step(_dev(inputs[0][t]), _dev(inputs[1][t]), actions, _dev(inputs[3][t]), _dev(inputs[4][t]))
+        ctx.eval_act(dev(obs[t]), dev(eps[t]) if t % 2 else None, actions)
+        ctx.eval_step(dev(inputs[0][t]), dev(inputs[1][t]), actions, dev(inputs[3][t]), dev(inputs[4][t]))
     assert ctx.eval_progress()[0] > 0
     ctx.eval_end()
     for a, b in zip(before, state(ctx)):
@@ -295,7 +330,7 @@ def test_evaluation_leaves_the_training_state_alone():
     sched = [O.sgd_schedule(rs, T * ctx.layout[p]["C"], 128, cfg.num_sgd_iter) for p in range(P)]
     for c in (ctx, twin):
         c.gae()
-        c.ppo_update((1 << P) - 1, [_dev(s[0]) for s in sched], [_dev(s[1]) for s in sched], [0.2] * P, max_steps=2)
+        c.ppo_update((1 << P) - 1, [dev(s[0]) for s in sched], [dev(s[1]) for s in sched], [0.2] * P, max_steps=2)
         c.synchronize()
     for p in range(P):
         assert not np.array_equal(ctx.params_get(p), before[3 + 10 * p + 1])   # the update moved them
@@ -329,7 +364,7 @@ def test_hostenv_loop_matches_stepwise(explore):
     obs = eb.reset_episodes()
     dsum, host_dist, steps_b = np.zeros(n), [[] for _ in range(n)], 0
     while steps_b < max_steps:
-        cb.eval_act(_dev(obs), eps[steps_b] if explore else None, actions)
+        cb.eval_act(dev(obs), eps[steps_b] if explore else None, actions)
         cb.synchronize()
         eb.act[:] = actions.cpu().numpy()
         eb.step()
@@ -337,7 +372,7 @@ def test_hostenv_loop_matches_stepwise(explore):
         for e in np.flatnonzero(eb.done):
             host_dist[e].append(dsum[e])
             dsum[e] = 0.0
-        cb.eval_step(_dev(eb.fw.copy()), _dev(eb.cfrc.copy()), actions, _dev(eb.kin.copy()), _dev(eb.done.copy()))
+        cb.eval_step(dev(eb.fw.copy()), dev(eb.cfrc.copy()), actions, dev(eb.kin.copy()), dev(eb.done.copy()))
         cb.synchronize()
         obs = eb.obs.copy()
         steps_b += 1

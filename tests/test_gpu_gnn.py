@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 from oracle import ddrl_oracle as O
-from tests.gpu_harness import (GNN_ENV, GnnOracleRollout, init_gnn_params, make_ctx, run_rollout,
-                                strict_params_check)
+from tests.gpu_harness import (GNN_ENV, GnnOracleRollout, filter_state, init_gnn_params, make_ctx, run_rollout,
+                               strict_params_check)
 
 pytestmark = pytest.mark.gpu
 SHAPES = O.gnn_param_shapes(4)
@@ -28,15 +28,11 @@ def _close(a, b, rtol=1e-5, atol=1e-5, msg=""):
     np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
 
 
-def _filt(D, rng):
-    return (1000.0, rng.normal(size=D) * 0.3, np.abs(rng.normal(size=D)) * 999.0 + 10.0)
-
-
 def _rollout(n, T, seed, head_scale, config=None):
     ctx, cfg, inst = make_ctx(GNN_ENV, n, T, config)
     rng = np.random.default_rng(seed)
     params = init_gnn_params(ctx, seed + 1, head_scale=head_scale)
-    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T,
+    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T,
                                            orc_cls=GnnOracleRollout)
     return ctx, cfg, orc, norms, params, a_gpu, a_orc
 

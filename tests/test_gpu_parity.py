@@ -15,7 +15,7 @@ import pytest
 
 from ddrl_amd import native as N
 from oracle import ddrl_oracle as O
-from tests.gpu_harness import init_params, make_ctx, run_rollout, strict_params_check
+from tests.gpu_harness import filter_state, init_params, make_ctx, run_rollout, strict_params_check
 
 pytestmark = pytest.mark.gpu
 RT, AT = 1e-5, 1e-5
@@ -32,10 +32,6 @@ def _gpu():
 
 def _close(a, b, rtol=RT, atol=AT, msg=""):
     np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
-
-
-def _filt(D, rng):
-    return (1000.0, rng.normal(size=D) * 0.3, np.abs(rng.normal(size=D)) * 999.0 + 10.0)
 
 
 ROLLOUT_ENVS = [
@@ -83,7 +79,7 @@ def _rollout_gae_parity(env, n, T, config):
         assert cfg.reward_mode == N.REWARD_NORM and inst.reward_mode == "norm"
     rng = np.random.default_rng(11)
     params = init_params(ctx, cfg, 3)
-    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T)
+    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T)
     _close(a_gpu, a_orc, msg="env actions")
     fn, fM, fS = ctx.filter_get()
     assert fn == orc.rs.n
@@ -115,7 +111,7 @@ def test_rollout_with_policy_mean_std_filter(env, n, T):
     assert cfg.policy_filter == 1
     rng = np.random.default_rng(17)
     params = init_params(ctx, cfg, 4)
-    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T)
+    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T)
     _close(a_gpu, a_orc, msg="env actions")
     for p in range(cfg.n_policies):
         pn, pM, pS = ctx.policy_filter_get(p)
@@ -177,7 +173,7 @@ def test_ppo_update_parity(env, n, T, steps, config):
     ctx, cfg, inst = make_ctx(env, n, T, config)
     rng = np.random.default_rng(5)
     params = init_params(ctx, cfg, 7, head_scale=1.0)
-    orc, norms, _, _ = run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T)
+    orc, norms, _, _ = run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T)
     shuffles, perms, kls = [], [], []
     for p in range(cfg.n_policies):
         lay = ctx.layout[p]
@@ -222,7 +218,7 @@ def test_full_schedule_runs_and_stays_close():
     ctx, cfg, inst = make_ctx(env, n, T)
     rng = np.random.default_rng(9)
     params = init_params(ctx, cfg, 2, head_scale=1.0)
-    orc, norms, _, _ = run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T)
+    orc, norms, _, _ = run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T)
     sh, pe = O.sgd_schedule(np.random.default_rng(1), T * n, 128, 10)
     for p in range(4):
         ctx.records_set(p, orc.flat_records(p, ctx.layout[p]))
@@ -257,7 +253,7 @@ def test_ddp_grad_and_apply_match_fused_step():
     ctx, cfg, inst = make_ctx(env, n, T)
     rng = np.random.default_rng(4)
     params = init_params(ctx, cfg, 8, head_scale=1.0)
-    orc, norms, _, _ = run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T)
+    orc, norms, _, _ = run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T)
     lay = ctx.layout[0]
     ctx.records_set(0, orc.flat_records(0, lay))
     ctx.adv_norm_set(0, *norms[0])
@@ -321,7 +317,7 @@ def test_host_buffer_loop_matches_device_loop():
     ctx_d, cfg, inst = make_ctx(env, n, T)
     ctx_h, _, _ = make_ctx(env, n, T)
     rng = np.random.default_rng(12)
-    filt = _filt(cfg.obs_full_dim, rng)
+    filt = filter_state(cfg.obs_full_dim, rng)
     for c in (ctx_d, ctx_h):
         init_params(c, cfg, 4)
         c.filter_set(*filt)
@@ -363,7 +359,7 @@ def test_rollout_fragment_matches_step_loop():
     ctx_a, cfg, inst = make_ctx(env, n, T)
     ctx_b, _, _ = make_ctx(env, n, T)
     rng = np.random.default_rng(21)
-    filt = _filt(cfg.obs_full_dim, rng)
+    filt = filter_state(cfg.obs_full_dim, rng)
     for c in (ctx_a, ctx_b):
         init_params(c, cfg, 5)
         c.filter_set(*filt)

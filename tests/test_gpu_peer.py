@@ -23,7 +23,7 @@ import numpy as np
 import pytest
 
 from oracle import ddrl_oracle as O
-from tests.gpu_harness import init_params, make_ctx, run_rollout
+from tests.gpu_harness import filter_state, init_params, make_ctx, run_rollout
 
 pytestmark = pytest.mark.gpu
 ENV = "QuantrupedMultiEnv_SharedDecentral"
@@ -37,15 +37,11 @@ def _gpu():
         pytest.skip("no GPU")
 
 
-def _filt(D, rng):
-    return (1000.0, rng.normal(size=D) * 0.3, np.abs(rng.normal(size=D)) * 999.0 + 10.0)
-
-
 def _rank_records(seed):
     ctx, cfg, inst = make_ctx(ENV, N_ENVS, T)
     params = init_params(ctx, cfg, 7, head_scale=1.0)      # the same weights on both ranks
     rng = np.random.default_rng(seed)
-    run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T)
+    run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T)
     return ctx, cfg, ctx.records_get(0)
 
 

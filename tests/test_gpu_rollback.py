@@ -23,7 +23,7 @@ import socket
 import numpy as np
 import pytest
 
-from tests.gpu_harness import init_params, make_ctx, run_rollout
+from tests.gpu_harness import filter_state, init_params, make_ctx, run_rollout
 
 pytestmark = pytest.mark.gpu
 ENV = "QuantrupedMultiEnv_Local"
@@ -34,10 +34,6 @@ def _gpu():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-def _filt(D, rng):
-    return (1000.0, rng.normal(size=D) * 0.3, np.abs(rng.normal(size=D)) * 999.0 + 10.0)
 
 
 def _ctx(env=ENV, n=32, T=8, **envvars):
@@ -73,7 +69,7 @@ def _schedule(ctx, P, seed=3):
 def _prepare(ctx, cfg, inst, seed=7):
     rng = np.random.default_rng(seed)
     params = init_params(ctx, cfg, seed, head_scale=1.0)
-    run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), cfg.frag_len)
+    run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), cfg.frag_len)
 
 
 def test_failed_fused_update_leaves_state_unchanged():

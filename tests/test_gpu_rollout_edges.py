@@ -19,7 +19,7 @@ import pytest
 from ddrl_amd import native as N
 from oracle import ddrl_oracle as O
 from tests import rollout_edge_inputs as E
-from tests.gpu_harness import OracleRollout, init_params, make_ctx, run_rollout, synthetic_inputs
+from tests.gpu_harness import OracleRollout, dev, filter_state, init_params, make_ctx, run_rollout, synthetic_inputs
 
 pytestmark = pytest.mark.gpu
 CENTRAL, SHARED, LOCAL, GLOBALCOST = E.CENTRAL, E.SHARED, E.LOCAL, E.GLOBALCOST
@@ -37,15 +37,6 @@ def _gpu():
 
 def _close(a, b, rtol=1e-5, atol=1e-5, msg=""):
     np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
-
-
-def _filt(D, rng):
-    return (1000.0, rng.normal(size=D) * 0.3, np.abs(rng.normal(size=D)) * 999.0 + 10.0)
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _check_adv_sums(ctx, p, T, msg=""):
@@ -119,7 +110,7 @@ def test_policy_mean_std_filter_multi_unit(env, n):
     assert cfg.policy_filter == 1
     rng = np.random.default_rng(17)
     params = init_params(ctx, cfg, 4)
-    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, _filt(cfg.obs_full_dim, rng), T)
+    orc, norms, a_gpu, a_orc = run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T)
     _close(a_gpu, a_orc, msg="env actions")
     for p in range(cfg.n_policies):
         pn, pM, pS = ctx.policy_filter_get(p)
@@ -157,7 +148,7 @@ def _observed_rows(ctx, cfg, obs):
     """observe, then act at t = 0: the normalized, routed rows as the record holds them."""
     import torch
     n = cfg.n_envs
-    ctx.observe(_dev(obs))
+    ctx.observe(dev(obs))
     eps = torch.zeros((n, cfg.n_agents, cfg.act_dim), dtype=torch.float32, device="cuda")
     actions = torch.zeros((n, 8), dtype=torch.float32, device="cuda")
     ctx.act(0, eps, actions)
@@ -229,7 +220,7 @@ def test_env_filter_disabled():
     ctx, cfg, inst, params, route = _filter_ctx(n, {"env_config": {"observation_filter_env": False}})
     assert cfg.filter_enabled == 0
     rng = np.random.default_rng(31)
-    filt = _filt(cfg.obs_full_dim, rng)
+    filt = filter_state(cfg.obs_full_dim, rng)
     ctx.filter_set(*filt)
     ctx.filter_delta_reset()
     obs = synthetic_inputs(rng, cfg, 1)[0][0]
@@ -251,7 +242,7 @@ def test_filter_clip_values(clip):
     ctx, cfg, inst, params, route = _filter_ctx(n, {"env_config": {"filter_clip": clip}})
     assert cfg.filter_clip == clip
     rng = np.random.default_rng(37)
-    filt = _filt(cfg.obs_full_dim, rng)
+    filt = filter_state(cfg.obs_full_dim, rng)
     ctx.filter_set(*filt)
     obs = synthetic_inputs(rng, cfg, 1)[0][0]
     for j in range(0, 43, 4):    # two outliers per column: z = sqrt(1257 / 2) = 25 whatever the spread
@@ -293,7 +284,7 @@ def test_filter_hard_columns(kind):
     rs = O.RunningStat((D,))
     rs.n, rs.M[:], rs.S[:] = int(prior[0]), prior[1], prior[2]
     for k in range(pushes):
-        ctx.observe(_dev(obs[k]))
+        ctx.observe(dev(obs[k]))
         for row in obs[k]:
             rs.push(row)
     ctx.synchronize()

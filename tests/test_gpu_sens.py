@@ -19,7 +19,8 @@ from ddrl_amd.spec import make_cfg
 from oracle import ddrl_oracle as O
 from tests import eval_reference as R
 from tests import sens_reference as S
-from tests.gpu_harness import GNN_ENV, OracleRollout, init_cup_params, init_params, run_rollout, synthetic_inputs
+from tests.gpu_harness import (GNN_ENV, OracleRollout, dev, init_params, init_policy_params, run_rollout,
+                               synthetic_inputs)
 
 pytestmark = pytest.mark.gpu
 PARITY = dict(rtol=1e-5, atol=2e-5)
@@ -40,15 +41,6 @@ def _ctx(env, n, config=None, frag=T):
     import torch
     cfg, inst = make_cfg(env, n, frag, config)
     return N.Context(cfg, 0, torch.cuda.current_stream().cuda_stream), cfg, inst
-
-
-def _init(ctx, cfg, seed, cup):
-    return init_cup_params(ctx, cfg, seed, head_scale=1.0) if cup else init_params(ctx, cfg, seed, head_scale=1.0)
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _means_bufs(ctx, cfg):
@@ -83,7 +75,7 @@ def _grid_run(name, compare_act):
     if grid:
         os.environ["DDRL_SENS_GRID"] = str(grid)
     try:
-        _init(ctx, cfg, 5, S.is_cup(config))
+        init_policy_params(ctx, cfg, 5, S.is_cup(config))
         rng = np.random.default_rng(3)
         if cfg.policy_filter:
             for p, st in enumerate(S.pfilt(cfg, rng)):
@@ -95,7 +87,7 @@ def _grid_run(name, compare_act):
         ctx.eval_sens_begin(steps)
         means, bad = [], []
         for t in range(T):
-            o_t = _dev(obs[t])
+            o_t = dev(obs[t])
             bufs = _means_bufs(ctx, cfg)
             ctx.eval_act(o_t, None, act)
             ctx.eval_sens(o_t, bufs)
@@ -123,7 +115,7 @@ def _grid_run(name, compare_act):
                             assert np.all(moved[:, col].astype(np.float64) ==
                                           obs[t][:, col].astype(np.float64) + (steps[p][f] if sign else -steps[p][f]))
                             lg = torch.full((ctx.layout[p]["C"], 2 * A), float("nan"), dtype=torch.float32, device="cuda")
-                            ctx.eval_act(_dev(moved), None, act, [lg if q == p else None for q in range(cfg.n_policies)])
+                            ctx.eval_act(dev(moved), None, act, [lg if q == p else None for q in range(cfg.n_policies)])
                             jobs.append((p, s, k, f, sign))
                             outs.append(lg)
             ctx.synchronize()
@@ -183,7 +175,7 @@ def test_matrices_match_the_oracle(name):
     env, n, config, grid = ORACLE_CASES[name]
     _, inst, config, filt, pfilt, obs, steps = S.oracle_case(name)
     ctx, cfg, _ = _ctx(env, n, config)
-    params = _init(ctx, cfg, 5, S.is_cup(config))
+    params = init_policy_params(ctx, cfg, 5, S.is_cup(config))
     orc = S.make_oracle(cfg, inst, config, params, filt, pfilt)
     ctx.filter_set(*filt)
     for p, st in enumerate(pfilt or []):
@@ -198,7 +190,7 @@ def test_matrices_match_the_oracle(name):
         ctx.eval_sens_begin(steps)
         inside = total = 0
         for t in range(T):
-            o_t = _dev(obs[t])
+            o_t = dev(obs[t])
             bufs = _means_bufs(ctx, cfg)
             ctx.eval_act(o_t, None, act)
             ctx.eval_sens(o_t, bufs)
@@ -234,7 +226,7 @@ def test_quota_gate_follows_the_episode_table():
     import torch
     n, E, steps_n = 37, 2, 12
     ctx, cfg, inst = _ctx("QuantrupedMultiEnv_Local", n, None, frag=4)
-    params = _init(ctx, cfg, 9, False)
+    params = init_policy_params(ctx, cfg, 9, False)
     rng = np.random.default_rng(43)
     filt = S.filt(cfg.obs_full_dim, rng)
     obs, _, fw, cfrc, _ = synthetic_inputs(rng, cfg, steps_n)
@@ -251,11 +243,11 @@ def test_quota_gate_follows_the_episode_table():
     ctx.eval_begin(E, filter_update=False)
     ctx.eval_sens_begin(hs)
     for t in range(steps_n):
-        o_t = _dev(obs[t])
+        o_t = dev(obs[t])
         bufs = _means_bufs(ctx, cfg)
         ctx.eval_act(o_t, None, act)
         ctx.eval_sens(o_t, bufs)
-        ctx.eval_step(_dev(fw[t]), _dev(cfrc[t]), _dev(actions[t]), _dev(kin[t]), _dev(done[t]))
+        ctx.eval_step(dev(fw[t]), dev(cfrc[t]), dev(actions[t]), dev(kin[t]), dev(done[t]))
         env_open = np.array(acc.count) < E
         ref.step([w[0] for w in S.sens_means(orc, obs[t], hs)], env_open)
         own.step([b.cpu().numpy() for b in bufs], env_open)
@@ -309,9 +301,9 @@ def test_sensitivity_leaves_the_training_state_alone():
     ctx.eval_begin(2, filter_update=False)
     ctx.eval_sens_begin([np.full(cfg.obs_dim[p], 0.1) for p in range(P)])
     for t in range(6):
-        ctx.eval_act(_dev(obs[t]), None, actions)
-        ctx.eval_sens(_dev(obs[t]), _means_bufs(ctx, cfg) if t % 2 else None)
-        ctx.eval_step(_dev(fw[t]), _dev(cfrc[t]), actions, _dev(kin[t]), _dev(done[t]))
+        ctx.eval_act(dev(obs[t]), None, actions)
+        ctx.eval_sens(dev(obs[t]), _means_bufs(ctx, cfg) if t % 2 else None)
+        ctx.eval_step(dev(fw[t]), dev(cfrc[t]), actions, dev(kin[t]), dev(done[t]))
     assert ctx.eval_sens_results(0)[2] > 0
     ctx.eval_end()
     for a, b in zip(before, state(ctx)):
@@ -320,7 +312,7 @@ def test_sensitivity_leaves_the_training_state_alone():
     sched = [O.sgd_schedule(rs, frag * ctx.layout[p]["C"], 128, cfg.num_sgd_iter) for p in range(P)]
     for c in (ctx, twin):
         c.gae()
-        c.ppo_update((1 << P) - 1, [_dev(s[0]) for s in sched], [_dev(s[1]) for s in sched], [0.2] * P, max_steps=2)
+        c.ppo_update((1 << P) - 1, [dev(s[0]) for s in sched], [dev(s[1]) for s in sched], [0.2] * P, max_steps=2)
         c.synchronize()
     for p in range(P):
         assert not np.array_equal(ctx.params_get(p), before[3 + 10 * p + 1])   # the update moved them

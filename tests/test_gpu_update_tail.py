@@ -19,7 +19,7 @@ import pytest
 
 from oracle import ddrl_oracle as O
 from tests import test_gpu_parity as TP
-from tests.gpu_harness import init_params, make_ctx, run_rollout, strict_params_check
+from tests.gpu_harness import filter_state, init_params, make_ctx, run_rollout, strict_params_check
 
 pytestmark = pytest.mark.gpu
 STEPS = 4
@@ -39,7 +39,7 @@ def _setup(env, n, T, config):
     ctx, cfg, inst = make_ctx(env, n, T, config)
     rng = np.random.default_rng(5)
     params = init_params(ctx, cfg, 7, head_scale=1.0)
-    orc, norms, _, _ = run_rollout(ctx, cfg, inst, params, rng, TP._filt(cfg.obs_full_dim, rng), T)
+    orc, norms, _, _ = run_rollout(ctx, cfg, inst, params, rng, filter_state(cfg.obs_full_dim, rng), T)
     for p in range(cfg.n_policies):
         # feed the ORACLE's batch so the update parity does not inherit rollout rounding
         ctx.records_set(p, orc.flat_records(p, ctx.layout[p]))
