@@ -231,14 +231,26 @@ __device__ __forceinline__ int wbase(int r) {
   return lrow<PAD>(c) + ((4 * q + r) ^ swz<PAD>(c));
 }
 
+// Phase marks of the forwards below (0: layer 1 done, 1: its tanh done, 2: layer 2 done): a
+// no-op everywhere but in the update kernel's stamped diagnostic build.
+struct FwdNoMark {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+
 // Forward of one branch for RT row tiles (16 rows each) of this wave.
 //   xop[t][s] : B operand of layer 1 at k-step s for row tile t, X[row = c][f = 4s + q]
 //   KS1       : k-steps of layer 1 (ceil(d / 4)); W1 rows beyond d are zero in LDS
 // Outputs h1[t][4], h2[t][4] (transposed activation tiles), out[t][O] (same in the 4 q-lanes).
 // Every weight operand read from LDS feeds RT MFMAs.
-template <int O, int KS1, int RT, bool PAD = kLdsPad>
+// HEADPF (branches of the fused row-split update kernels with at most 4 outputs): the head's Wo
+// rows are read ahead -- rows 0 - 7 before layer 2's tanh, rows 8 - 15 before the first rows'
+// FMAs -- instead of each right before its FMAs, where a single wave per SIMD pays the LDS latency
+// once per row.  Same chains, same bits.  The rows stay live in 16 O registers, which is why wider
+// heads do not take it.
+template <int O, int KS1, int RT, bool PAD = kLdsPad, class Mark = FwdNoMark, bool HEADPF = false>
 __device__ __forceinline__ void ffn_fwd_rt(const NetLds& W, const float (*xop)[12],
-                                           floatx4 (*h1)[4], floatx4 (*h2)[4], float (*out)[O]) {
+                                           floatx4 (*h1)[4], floatx4 (*h2)[4], float (*out)[O],
+                                           Mark mark = Mark()) {
   constexpr int BLK = lds_blk(PAD);
   const int lane = threadIdx.x & 63, q = lane >> 4, c = lane & 15;
 #pragma unroll
@@ -282,6 +294,7 @@ __device__ __forceinline__ void ffn_fwd_rt(const NetLds& W, const float (*xop)[1
       __builtin_amdgcn_sched_barrier(0);
     }
   }
+  mark(0);
   float wq[3][4];
   ld2(0, wq[0]);
   ld2(1, wq[1]);
@@ -291,6 +304,7 @@ __device__ __forceinline__ void ffn_fwd_rt(const NetLds& W, const float (*xop)[1
     for (int ob = 0; ob < 4; ++ob)
 #pragma unroll
       for (int r = 0; r < 4; ++r) h1[t][ob][r] = tanh_fast(h1[t][ob][r]);
+  mark(1);
 
 #pragma unroll
   for (int ob = 0; ob < 4; ++ob) {
@@ -309,6 +323,41 @@ __device__ __forceinline__ void ffn_fwd_rt(const NetLds& W, const float (*xop)[1
         for (int t = 0; t < RT; ++t) h2[t][ob] = mfma4(wq[k % 3][ob], h1[t][k >> 2][k & 3], h2[t][ob]);
       __builtin_amdgcn_sched_barrier(0);
     }
+  }
+  mark(2);
+  if constexpr (HEADPF) {
+    float wa[8][O], wb[8][O], acc[RT][O];
+    auto ld_wo = [&](int k, float* a) {   // row (fb, r) = 4 fb + r of this lane's 16 features
+      const float* wp = W.wo + (16 * (k >> 2) + 4 * q + (k & 3)) * O;
+#pragma unroll
+      for (int o = 0; o < O; ++o) a[o] = wp[o];
+    };
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ld_wo(k, wa[k]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+      for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) h2[t][ob][r] = tanh_fast(h2[t][ob][r]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ld_wo(8 + k, wb[k]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+      for (int o = 0; o < O; ++o) {
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) a = fmaf(h2[t][k >> 2][k & 3], k < 8 ? wa[k][o] : wb[k - 8][o], a);
+        acc[t][o] = a;
+      }
+#pragma unroll
+    for (int o = 0; o < O; ++o)
+#pragma unroll
+      for (int t = 0; t < RT; ++t) out[t][o] = qsum(acc[t][o]) + W.bo[o];
+    return;
   }
 #pragma unroll
   for (int t = 0; t < RT; ++t)

@@ -44,6 +44,18 @@
 // Fused launches exchange LSB-tagged quads (round 4), except under the atomic protocol, which
 // keeps the {value, tag} pairs everywhere
 #define DDRL_LX_ON (!DDRL_XCHG_IS_ATOMIC || DDRL_XCHG_LXSYS)
+// The fused row-split kernels of ppo_ffn.hip read the head's Wo rows ahead of the forward's tail
+// (ffn_fwd_rt's HEADPF, common.h) in every branch with at most DDRL_HEAD_PF outputs -- the value
+// branches and the A = 2 policy branches -- except the cup model's policy branch.  Measured per
+// instance: with 8 outputs (the A = 4 policy branch) the 128 row values held
+// live cost 55 more spill slots and 4.6 % of the step, and the cup policy branch lost 1.2 %.  The
+// atomic, peer and KSP = 1 translation units keep the plain tail.  The results are the same bits
+// either way (tests/test_gpu_update_fwd.py).  -DDDRL_HEAD_PF=0 builds the plain tail here for A/B
+// timing, =8 includes the A = 4 policy branches.
+#ifndef DDRL_HEAD_PF
+#define DDRL_HEAD_PF 4
+#endif
+constexpr int kHeadPfMaxO = (DDRL_FFN_KSP == 2 && !DDRL_FFN_AT) ? DDRL_HEAD_PF : 0;
 
 namespace {
 
@@ -424,17 +436,30 @@ __device__ __forceinline__ int perm_slot(const UpdateArgs& U, int step) {
 #ifdef DDRL_STAMPS
 __device__ unsigned long long g_stamps[32][16];
 __device__ unsigned g_poll_stale[32][8];   // first partner polls that missed, per workgroup and wave
-#define STAMP_INIT unsigned long long st_prev = __builtin_amdgcn_s_memtime(), st_acc[16] = {0};
+// Splits of the forward stamp (phase 0), in time order: [0] layer 1 (to the fence behind its
+// last MFMA), [1] from there to the fence behind layer 1's tanh in source order (what the
+// scheduler left between the two fences: part of the tanh moves into layer 2's first k-steps),
+// [2] from there to the fence behind layer 2's last MFMA, [3] the tail (layer 2's tanh, head,
+// cup).  What phase 0 holds before the forward (Adam's alpha, load_row) is the remainder.
+// tools/diag_stamps.py prints the slots in this order.
+__device__ unsigned long long g_fwd_stamps[32][4];
+#define STAMP_INIT unsigned long long st_prev = __builtin_amdgcn_s_memtime(), st_acc[16] = {0}, st_fprev = 0, st_f[4] = {0}; \
+  auto fwd_mark = [&](int k_) { if (tid == DDRL_STAMP_TID) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
+                                  if (k_ >= 0) st_f[k_] += t_ - st_fprev; st_fprev = t_; } };
 #ifndef DDRL_STAMP_TID   // the stamped thread (lane 0 of a wave): per-wave diagnostic builds
 #define DDRL_STAMP_TID 0
 #endif
 #define STAMP(k) do { if (tid == DDRL_STAMP_TID) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_prev; st_prev = t_; } } while (0)
-#define STAMP_DONE do { if (tid == DDRL_STAMP_TID) for (int k_ = 0; k_ < 16; ++k_) g_stamps[blockIdx.x][k_] = st_acc[k_]; \
+#define STAMP_DONE do { if (tid == DDRL_STAMP_TID) { for (int k_ = 0; k_ < 16; ++k_) g_stamps[blockIdx.x][k_] = st_acc[k_]; \
+                                                     for (int k_ = 0; k_ < 4; ++k_) g_fwd_stamps[blockIdx.x][k_] = st_f[k_]; } \
                         if (lane == 0) g_poll_stale[blockIdx.x][w & 7] = st_stale; } while (0)
 }  // namespace
 #if !DDRL_FFN_AT && DDRL_FFN_KSP != 1
 extern "C" int ddrl_diag_stamps(unsigned long long* host) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(g_stamps)) == hipSuccess ? 0 : -1;
+}
+extern "C" int ddrl_diag_fwd_stamps(unsigned long long* host) {
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fwd_stamps), sizeof(g_fwd_stamps)) == hipSuccess ? 0 : -1;
 }
 extern "C" int ddrl_diag_poll_stale(unsigned* host) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_poll_stale), sizeof(g_poll_stale)) == hipSuccess ? 0 : -1;
@@ -442,7 +467,7 @@ extern "C" int ddrl_diag_poll_stale(unsigned* host) {
 #endif
 namespace {
 #else
-#define STAMP_INIT
+#define STAMP_INIT const FwdNoMark fwd_mark;
 #define STAMP(k)
 #define STAMP_DONE
 #endif
@@ -934,7 +959,10 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     // ---- forward + loss + output gradient (two row tiles) ----
     floatx4 h1[RT][4], h2[RT][4], dz[RT][4];
     float out[RT][OB], dout[RT][OB];
-    ffn_fwd_rt<OB, KS1, RT, PAD>(W, cur.x, h1, h2, out);
+    fwd_mark(-1);
+    if constexpr (KSP == 2 && RT == 1 && OB <= kHeadPfMaxO && !(CUP && POL))
+      ffn_fwd_rt<OB, KS1, RT, PAD, decltype(fwd_mark), true>(W, cur.x, h1, h2, out, fwd_mark);
+    else ffn_fwd_rt<OB, KS1, RT, PAD>(W, cur.x, h1, h2, out, fwd_mark);
     // "cup" (coupling_net_glorot_uniform_init.py:22-30): means scaled by the record's leg row
     float pre[RT][A], cf[RT][A];
     if constexpr (cup) {
@@ -949,6 +977,7 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
           }
       }
     }
+    fwd_mark(3);
     STAMP(0);
     float st[NSTAT];
 #pragma unroll

@@ -39,23 +39,29 @@ def run(n, variants):
         print(f"{v or 'baseline':28s} {out.stdout.strip()} {out.stderr.strip()[-200:]}", flush=True)
 
 
-def one(lib, n, env="QuantrupedMultiEnv_Local"):
+def one(lib, n, env="QuantrupedMultiEnv_Local", model=""):
     """us per sequential minibatch step of the fused update of `env` (Local: 4 policies, d = 35;
-    SharedDecentral: 1 policy over 4 leg agents, d = 19) at n envs, T = 200."""
+    SharedDecentral: 1 policy over 4 leg agents, d = 19; any registered fcnet env, its action width
+    from the cfg) at n envs, T = 200; model "cup": the leg-coupling model of the LegID env."""
     import numpy as np, torch
     from ddrl_amd import native as N
     N.load(lib)
     from ddrl_amd.spec import make_cfg
-    from ddrl_amd.trainer import glorot_ffn_flat
+    from ddrl_amd.trainer import glorot_ffn_flat, leg_coupling_init
     T = 200
-    cfg, _ = make_cfg(env, n, T)
-    P = cfg.n_policies
+    cfg, _ = make_cfg(env, n, T, {"model": {"custom_model": model}} if model else None)
+    P, A = cfg.n_policies, cfg.act_dim
     ctx = N.Context(cfg, 0, torch.cuda.current_stream().cuda_stream)
     rng = np.random.default_rng(0)
     for p in range(P):
-        ctx.params_set(p, glorot_ffn_flat(rng, cfg.obs_dim[p], 2))
+        flat = glorot_ffn_flat(rng, cfg.obs_dim[p], A)
+        if model == "cup":
+            flat = np.concatenate([flat, np.asarray(leg_coupling_init(A), np.float32).reshape(-1)])
+        ctx.params_set(p, flat)
         lay = ctx.layout[p]
         r = rng.normal(size=(T * lay["C"], lay["stride"])).astype(np.float32) * 0.5
+        if lay["leg"] >= 0:   # the record's leg row indexes the coupling table
+            r[:, lay["leg"]] = np.arange(r.shape[0]) % 4
         ctx.records_set(p, r)
     R = T * ctx.layout[0]["C"]
     nb = R // 128
@@ -84,4 +90,4 @@ if __name__ == "__main__":
     elif sys.argv[1] == "run":
         run(int(sys.argv[2]) if len(sys.argv) > 2 else 512, sys.argv[3:] or VARIANTS)
     else:
-        one(sys.argv[2], int(sys.argv[3]), *sys.argv[4:5])
+        one(sys.argv[2], int(sys.argv[3]), *sys.argv[4:6])

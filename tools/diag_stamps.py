@@ -62,8 +62,19 @@ if hasattr(N.load(), "ddrl_diag_poll_stale"):
     ps = np.array(ps, dtype=np.float64).reshape(32, 8)
     for b in range(0, 32, 8):
         print(f"block {b:2d}: first poll stale, waves 0-3: " + " ".join(f"{100 * x / steps:5.1f}%" for x in ps[b, :4]))
+fw = None
+if hasattr(N.load(), "ddrl_diag_fwd_stamps"):
+    # splits of the forward stamp, in time order: layer 1, layer 1 -> layer 2 gap, layer 2, tail
+    fs = (ctypes.c_ulonglong * (32 * 4))()
+    assert N.load().ddrl_diag_fwd_stamps(fs) == 0
+    fw = np.array(fs, dtype=np.float64).reshape(32, 4)[blocks] / steps
 for wg in range(len(blocks)):
     tot = a[wg].sum()
     print(f"{labels[wg]} WG: {tot:.0f} cycles/step")
     for k, nm in enumerate(names):
         print(f"   {nm:45s} {a[wg, k]:8.0f}  {100 * a[wg, k] / tot:5.1f}%")
+        if k == 0 and fw is not None:
+            head = a[wg, 0] - fw[wg].sum()
+            for nm2, v in [("step head (alpha, load_row)", head), ("layer 1", fw[wg, 0]), ("layer 1 -> layer 2 gap", fw[wg, 1]),
+                           ("layer 2", fw[wg, 2]), ("tail (tanh, head, cup)", fw[wg, 3])]:
+                print(f"      fwd: {nm2:38s} {v:8.0f}  {100 * v / tot:5.1f}%")
