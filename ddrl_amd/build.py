@@ -32,8 +32,13 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-I", INCLUDE,
 _ILP = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 _VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 #  * the atomic-protocol fallback likewise (its fused step 12.64 -> 12.25 us)
+#  * the 256-row kernels (two row tiles per wave): MFMA results in VGPRs, no ILP strategy -- the
+#    A = 2 and A = 4 instances spill nothing either way, the A = 8 ones 256 / 288 bytes of scratch
+#    per lane against 1808 / 1968 with it and 400 / 448 with neither flag (DESIGN.md section 3,
+#    "256-row minibatches")
 SRC_FLAGS = {"ppo_ffn.hip": _ILP + _VGPR_MFMA, "ppo_ffn_peer.hip": _ILP + _VGPR_MFMA, "gnn.hip": _VGPR_MFMA,
-             "ppo_ffn_atomic.hip": _VGPR_MFMA}
+             "ppo_ffn_atomic.hip": _VGPR_MFMA, "ppo_ffn_mb256.hip": _VGPR_MFMA,
+             "ppo_ffn_mb256_atomic.hip": _VGPR_MFMA}
 
 
 def _sources():

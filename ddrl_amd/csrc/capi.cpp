@@ -193,7 +193,12 @@ static int validate(const ddrl_cfg& c) {
   if (c.n_agents < 1 || c.n_agents > DDRL_MAXAG) return fail("n_agents must be in [1, 4]");
   if (c.act_dim != 2 && c.act_dim != 4 && c.act_dim != 8) return fail("act_dim must be 2, 4 or 8");
   if (c.obs_full_dim < 1 || c.obs_full_dim > DDRL_MAXFULL) return fail("obs_full_dim out of range");
-  if (c.sgd_minibatch_size != 128) return fail("sgd_minibatch_size must be 128 (fused kernel tile)");
+  // the fused update kernels are built per minibatch size: 128 rows for every model, 256 for the
+  // fcnet models (ppo_ffn_mb256.hip)
+  if (c.model_kind == DDRL_MODEL_GNN && c.sgd_minibatch_size != 128)
+    return fail("sgd_minibatch_size must be 128 for the GraphNet model (its update kernels are built for 128 rows)");
+  if (c.sgd_minibatch_size != 128 && c.sgd_minibatch_size != 256)
+    return fail("sgd_minibatch_size must be 128 or 256 (the fused update kernels are built for these two)");
   if (c.num_sgd_iter < 1) return fail("num_sgd_iter must be >= 1");
   for (int j = 0; j < c.n_agents; ++j)
     if (c.agent_policy[j] < 0 || c.agent_policy[j] >= c.n_policies) return fail("bad agent_policy");
@@ -236,13 +241,18 @@ const char* ddrl_last_error(void) { return g_err.c_str(); }
 int ddrl_ctx_create(const ddrl_cfg* cfg, int device, ddrl_ctx** out) {
   if (!cfg || !out) return fail("null argument");
   if (validate(*cfg)) return -1;
+  // fused update geometry: DDRL_UPDATE_SPLIT=1 keeps one workgroup per branch (timing / A-B)
+  int update_split = 2;
+  if (const char* e = std::getenv("DDRL_UPDATE_SPLIT")) update_split = std::atoi(e) == 1 ? 1 : 2;
+  if (update_split != 2 && cfg->sgd_minibatch_size != 128)
+    return fail("sgd_minibatch_size 256 needs the row split: DDRL_UPDATE_SPLIT=1 would put 256-row images in one "
+                "workgroup, which its LDS cannot hold");
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail("device index out of range");
   HIPCHK(hipSetDevice(device));
   ddrl_ctx* c = new ddrl_ctx();
-  // fused update geometry: DDRL_UPDATE_SPLIT=1 keeps one workgroup per branch (timing / A-B)
-  if (const char* e = std::getenv("DDRL_UPDATE_SPLIT")) c->update_split = std::atoi(e) == 1 ? 1 : 2;
+  c->update_split = update_split;
   c->cfg = *cfg;
   c->device = device;
   const ddrl_cfg& g = c->cfg;
@@ -493,7 +503,11 @@ static void launch_ffn(ddrl_ctx* c, const UpdateArgs* ua, const UpdateHyper& h, 
   // exchange abandoned in its first step would leave it -- every workgroup runs its steps and
   // none writes back (no per-step cost in the kernel; a compare per step measured 0.18 us)
   if (c->fail_step >= 0 && !ua->grad_out) (void)hipMemsetD32Async((hipDeviceptr_t)c->err, 1, 1, c->stream);
-  (c->xchg_atomic ? launch_update_ffn_atomic : launch_update_ffn)(
+  // a fused launch runs the kernels of the context's minibatch size; gradient-export launches
+  // carry at most 128 rows at either size and run the 128-row kernels
+  const bool mb256 = c->cfg.sgd_minibatch_size == 256 && !ua->grad_out;
+  (mb256 ? (c->xchg_atomic ? launch_update_ffn_mb256_atomic : launch_update_ffn_mb256)
+         : (c->xchg_atomic ? launch_update_ffn_atomic : launch_update_ffn))(
       c->stream, ua, h, nrows, inv_n, c->cfg.act_dim, d, stride, c->cfg.leg_coupling, c->xchg, c->gx, ksp, c->err,
       &c->upd_epoch, c->xcc, -1, 0u);
 }
@@ -1340,7 +1354,7 @@ int ddrl_ppo_update_from(ddrl_ctx* c, int mask, const int32_t* const* shuffle, c
     if (!(mask & (1 << p))) continue;
     if (!shuffle[p] || !perm[p]) return fail("null shuffle/perm for a masked policy");
     // every minibatch is a full slice of the shuffled batch (RLlib's multi-GPU loader refuses
-    // a batch smaller than one minibatch too); the kernels read shuffle[0 .. nb * 128)
+    // a batch smaller than one minibatch too); the kernels read shuffle[0 .. nb * sgd_minibatch_size)
     if (c->pol[p].R < c->cfg.sgd_minibatch_size)
       return fail("policy " + std::to_string(p) + ": the train batch holds " + std::to_string(c->pol[p].R) +
                   " rows, fewer than one minibatch (sgd_minibatch_size " +
@@ -1361,7 +1375,8 @@ int ddrl_ppo_update_from(ddrl_ctx* c, int mask, const int32_t* const* shuffle, c
   // the arguments travel by value in the kernel's argument block (no copy from this stack frame)
   if (c->cfg.model_kind == DDRL_MODEL_FFN) {
     if (snapshot(c, mask & ((1 << c->cfg.n_policies) - 1))) return -1;
-    launch_ffn(c, ua, h, 128, 1.f / c->cfg.sgd_minibatch_size, maxd, maxs, c->update_split, (1 << n) - 1);
+    launch_ffn(c, ua, h, c->cfg.sgd_minibatch_size, 1.f / c->cfg.sgd_minibatch_size, maxd, maxs, c->update_split,
+               (1 << n) - 1);
   }
   else if (c->pol[0].last_steps > 0) {   // one shared policy
     const int last = c->pol[0].last_steps;
@@ -1503,6 +1518,7 @@ int ddrl_ppo_update_ddp(ddrl_ctx* c, int pid, const int32_t* shuffle, const int3
   if (pid < 0 || pid >= c->cfg.n_policies) return fail("bad policy id");
   if (!c->comm) return fail("no communicator (ddrl_comm_init)");
   if (!shuffle || !perm || E < 1 || nb < 1) return fail("bad schedule");
+  // (sgd_minibatch_size 256: the split over two or more ranks fits, a whole minibatch per rank does not)
   if (m < 1 || m > 128) return fail("rows_per_rank must be in [1, 128]");
   if (stats_reserve(c, pid, (size_t)nb)) return -1;   // the last epoch's rows
   Policy& P = c->pol[pid];
@@ -1637,6 +1653,9 @@ int ddrl_peer_attach(ddrl_ctx* c, void* gx, int rank, int nranks) {
   if (nranks != 2 || rank < 0 || rank > 1) return fail("peer mode splits the minibatch over exactly two ranks");
   if (c->cfg.model_kind != DDRL_MODEL_FFN) return fail("peer mode is built for fcnet policies");
   if (c->update_split != 2) return fail("peer mode needs the row split (DDRL_UPDATE_SPLIT=2, the default)");
+  if (c->cfg.sgd_minibatch_size != DDRL_MB)
+    return fail("peer mode is built for sgd_minibatch_size 128 (64 rows per rank); this context has " +
+                std::to_string(c->cfg.sgd_minibatch_size));
   // rank 0 clears the outboxes (no launch of either rank may be in flight: after a failed update
   // both ranks have synchronized; rank 1 attaches after rank 0); both count launches from here
   if (rank == 0) HIPCHK(hipMemsetAsync(gx, 0, gx_bytes(DDRL_MAXP), c->stream));

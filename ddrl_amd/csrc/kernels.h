@@ -8,7 +8,7 @@
 #define DDRL_MAXD 48      // per-agent observation width
 #define DDRL_MAXFULL 48   // full observation width (43 / 44)
 #ifndef DDRL_MB
-#define DDRL_MB 128       // sgd_minibatch_size supported by the update kernels
+#define DDRL_MB 128       // sgd_minibatch_size of the update kernels (256: ppo_ffn_mb256.hip defines it first)
 #endif
 
 // Record (one training row) layout, in floats.  Rows are time-major:
@@ -235,6 +235,16 @@ void launch_update_ffn_k1(hipStream_t s, const UpdateArgs* ua, const UpdateHyper
 void launch_update_ffn_peer(hipStream_t s, const UpdateArgs* ua, const UpdateHyper& h, int nrows, float inv_n, int A,
                             int d, int stride, int cup, unsigned long long* xchg, unsigned long long* gx, int ksp,
                             int* err, unsigned* epoch_ctr, int* xcc, int own_kq = -1, unsigned lx_base = 0);
+// sgd_minibatch_size = 256 (ppo_ffn_mb256.hip / ppo_ffn_mb256_atomic.hip, the header built with
+// DDRL_MB = 256): fused row-split launches of whole minibatches only -- ksp = 2, nrows = 256, no
+// gradient export, own_kq = -1; anything else sets the error word and launches nothing
+void launch_update_ffn_mb256(hipStream_t s, const UpdateArgs* ua, const UpdateHyper& h, int nrows, float inv_n, int A,
+                             int d, int stride, int cup, unsigned long long* xchg, unsigned long long* gx, int ksp,
+                             int* err, unsigned* epoch_ctr, int* xcc, int own_kq = -1, unsigned lx_base = 0);
+void launch_update_ffn_mb256_atomic(hipStream_t s, const UpdateArgs* ua, const UpdateHyper& h, int nrows, float inv_n,
+                                    int A, int d, int stride, int cup, unsigned long long* xchg,
+                                    unsigned long long* gx, int ksp, int* err, unsigned* epoch_ctr, int* xcc,
+                                    int own_kq = -1, unsigned lx_base = 0);
 // epoch_ctr: per-context launch counter (granule tags)
 size_t gx_bytes(int P);
 // clip_by_global_norm + tf1 Adam on a flat (all-reduced) gradient vector

@@ -24,7 +24,22 @@
 #ifndef DDRL_FFN_KSP
 #define DDRL_FFN_KSP 0
 #endif
-#if DDRL_FFN_KSP == 1
+// Minibatches of 256 rows (-DDDRL_MB=256 ahead of this header: ppo_ffn_mb256.hip for the default
+// protocol, ppo_ffn_mb256_atomic.hip for the atomic one): only the fused row-split kernels, each
+// workgroup on 128 rows -- two 16-row tiles per wave, the geometry of the split-less A = 8 kernel.
+// Gradient-export launches of a 256 context carry at most 128 rows and stay with the 128 units.
+#if DDRL_MB == 256
+#if DDRL_FFN_KSP != 2 || DDRL_FFN_AT == 2
+#error "the DDRL_MB = 256 units build the fused row-split kernels only (DDRL_FFN_KSP = 2, no peer mode)"
+#endif
+#if DDRL_FFN_AT
+#define DDRL_FFN_LAUNCH launch_update_ffn_mb256_atomic
+#else
+#define DDRL_FFN_LAUNCH launch_update_ffn_mb256
+#endif
+#elif DDRL_MB != 128
+#error "DDRL_MB must be 128 or 256"
+#elif DDRL_FFN_KSP == 1
 #define DDRL_FFN_LAUNCH launch_update_ffn_k1
 #elif DDRL_FFN_AT == 2
 #define DDRL_FFN_LAUNCH launch_update_ffn_peer
@@ -88,7 +103,7 @@ __host__ __device__ constexpr int gx_pairs(int OB, int NW) {
 struct UpdateBatch {
   UpdateArgs a[DDRL_MAXP];   // one entry per policy, by value in the kernel argument block
   UpdateHyper h;
-  int nrows;             // rows per minibatch handled here (<= 128)
+  int nrows;             // rows per minibatch handled here (<= DDRL_MB)
   float inv_n;           // 1 / sgd_minibatch_size (global minibatch)
   unsigned long long* xchg;  // [P][2 branches][KSP][2 parities] tagged norm^2 granules
   unsigned long long* gx;    // [P][2 branches][KSP][2 parities][GX_MAX_PAIRS][256 lanes][2] partial-gradient granules
@@ -120,10 +135,13 @@ __device__ __forceinline__ bool bchk(bool ok, int k) {
 }
 }  // namespace
 #if !DDRL_FFN_AT
-#if DDRL_FFN_KSP == 2
+#if DDRL_FFN_KSP == 2 && DDRL_MB == 128
 extern "C" int ddrl_diag_bounds_k1(unsigned* host, int reset);
+extern "C" int ddrl_diag_bounds_mb256(unsigned* host, int reset);
 #endif
-#if DDRL_FFN_KSP == 1
+#if DDRL_MB == 256
+extern "C" int ddrl_diag_bounds_mb256(unsigned* host, int reset) {
+#elif DDRL_FFN_KSP == 1
 extern "C" int ddrl_diag_bounds_k1(unsigned* host, int reset) {
 #else
 extern "C" int ddrl_diag_bounds(unsigned* host, int reset) {
@@ -133,9 +151,11 @@ extern "C" int ddrl_diag_bounds(unsigned* host, int reset) {
     unsigned z[DDRL_NBOUNDS] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_bounds), z, sizeof(z)) != hipSuccess) return -1;
   }
-#if DDRL_FFN_KSP == 2   // the KSP = 1 kernels' counters (ppo_ffn_k1.hip) count too
-  unsigned k1[DDRL_NBOUNDS];
+#if DDRL_FFN_KSP == 2 && DDRL_MB == 128   // the KSP = 1 kernels' counters (ppo_ffn_k1.hip) count too,
+  unsigned k1[DDRL_NBOUNDS];              // and the 256-row kernels' (ppo_ffn_mb256.hip)
   if (ddrl_diag_bounds_k1(k1, reset) != 0) return -1;
+  for (int i = 0; i < DDRL_NBOUNDS; ++i) host[i] += k1[i];
+  if (ddrl_diag_bounds_mb256(k1, reset) != 0) return -1;
   for (int i = 0; i < DDRL_NBOUNDS; ++i) host[i] += k1[i];
 #endif
   return 0;
@@ -230,8 +250,13 @@ __device__ __forceinline__ void stage_branch_batched(const float* __restrict__ t
 // LDS floats of one branch's weight image (a multiple of 4 floats)
 __host__ __device__ constexpr int branch_lds_floats(bool pad) { return lds_img(48, pad) + lds_img(64, pad) + 128 + 64 * 16 + 16; }
 // the swizzled image layout of an update kernel (common.h): the padded one, except for the A = 8
-// kernel without the row split, whose LDS budget has room only for the compact images
-__host__ __device__ constexpr bool update_pad(int A, int ksp) { return kLdsPad && !(A == 8 && ksp == 1); }
+// kernels on 128 rows per workgroup (no row split at 128, the row split at 256), whose LDS budget
+// has room only for the compact images
+__host__ __device__ constexpr bool update_pad(int A, int ksp) { return kLdsPad && !(A == 8 && DDRL_MB / ksp >= 128); }
+// the policy head's gradient on the matrix cores, from two more feature-major images (HMF in
+// update_loop): the row split on 64 rows per workgroup.  With 128 rows the images pass the
+// 160 KB of a workgroup (183 KB for A = 2), so those kernels keep the DPP reductions
+__host__ __device__ constexpr bool update_hmf(int ksp) { return ksp == 2 && DDRL_MB / ksp == 64; }
 
 // "Small" parameters owned one per thread: [dWo 64*OB][dbo OB][db1 64][db2 64], then the
 // policy branch's leg-coupling table [4][A] of the "cup" model
@@ -454,7 +479,7 @@ __device__ unsigned long long g_fwd_stamps[32][4];
                                                      for (int k_ = 0; k_ < 4; ++k_) g_fwd_stamps[blockIdx.x][k_] = st_f[k_]; } \
                         if (lane == 0) g_poll_stale[blockIdx.x][w & 7] = st_stale; } while (0)
 }  // namespace
-#if !DDRL_FFN_AT && DDRL_FFN_KSP != 1
+#if !DDRL_FFN_AT && DDRL_FFN_KSP != 1 && DDRL_MB == 128
 extern "C" int ddrl_diag_stamps(unsigned long long* host) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(g_stamps)) == hipSuccess ? 0 : -1;
 }
@@ -837,11 +862,12 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
   float* Pb = bufB + 64 * LD;               // [NW][NSB] per-wave partial small grads
   float* red = Pb + NW * NSB;               // [NW][8] row-stat partials, [64..] scalars
   int* idxb = reinterpret_cast<int*>(red + 128);   // [128] record rows of the next step
+  static_assert(ROWS <= 128 && ROWS <= NT, "idxb holds 128 rows, one staging slot per thread");
   // policy branch of the row split: the head gradient dWo = H2^T dout runs on the matrix cores
   // with the dW2 tiles, from feature-major images of H2 and dout (rows >= 2A of the dout
   // image stay zero); the other instances reduce it with DPP transposes (their LDS budget --
   // A = 8, 128-row images -- has no room for the two images)
-  constexpr bool HMF = POL && KSP == 2;
+  constexpr bool HMF = POL && update_hmf(KSP);
   float* bufH = red + 256;                  // HMF: feature-major [64][LD] H2
   float* bufD = bufH + 64 * LD;             // HMF: feature-major [16][LD] dout
   float* stg = red + 256 + (HMF ? 80 * LD : 0);   // [ROWS][stride] records of the next step (16 B aligned)
@@ -1522,7 +1548,7 @@ static size_t update_lds_bytes(int O, int stride, int ksp) {
   const int nw = waves_for(O / 2, ksp);
   // + the policy head's H2 / dout images of the row split (HMF in update_loop)
   return (size_t)(branch_lds_floats(update_pad(O / 2, ksp)) + 2 * 64 * (DDRL_MB / ksp + 8) + nw * nsb + 256 +
-                  (ksp == 2 ? 80 * (DDRL_MB / ksp + 8) : 0) +
+                  (update_hmf(ksp) ? 80 * (DDRL_MB / ksp + 8) : 0) +
                   (DDRL_MB / ksp) * 4 * stg_chunks(stride, O / 2)) * 4;
 }
 
@@ -1546,7 +1572,15 @@ static void launch_update_t(hipStream_t s, UpdateBatch& ub, int P, int stride, i
 void DDRL_FFN_LAUNCH(hipStream_t s, const UpdateArgs* ua, const UpdateHyper& h, int nrows, float inv_n,
                        int A, int d, int stride, int cup, unsigned long long* xchg, unsigned long long* gx, int ksp,
                        int* err, unsigned* epoch_ctr, int* xcc, int own_kq, unsigned lx_base) {
-#if DDRL_FFN_KSP == 2
+#if DDRL_MB == 256
+  // only fused row-split launches of whole 256-row minibatches exist at this size.  The host
+  // (capi.cpp launch_ffn) sends nothing else here; were it to, the launch is dropped with the
+  // error word set, so the call fails and the state is restored: never another kernel in its place
+  if (!(ksp == 2 && ua[0].grad_out == nullptr && own_kq < 0 && nrows == DDRL_MB)) {
+    (void)hipMemsetD32Async((hipDeviceptr_t)err, 1, 1, s);
+    return;
+  }
+#elif DDRL_FFN_KSP == 2
   // only the fused row-split kernels (LSB quads) live here; the KSP = 1 kernels and the
   // gradient-export launches are built in ppo_ffn_k1.hip
   if (!(ksp == 2 && ua[0].grad_out == nullptr)) {

@@ -73,7 +73,8 @@ typedef struct ddrl_cfg {
   float lr, grad_clip;
   float adam_beta1, adam_beta2, adam_eps;
   int32_t vf_clip_mode;     /* DDRL_VF_CLIP_*                                               */
-  int32_t sgd_minibatch_size;  /* 128 (the fused update kernel is built for 128)          */
+  int32_t sgd_minibatch_size;  /* 128, or 256 for the fcnet models (the sizes the fused    */
+                               /* update kernels are built for); anything else is refused  */
   int32_t num_sgd_iter;        /* 10                                                       */
   int32_t act_negate[DDRL_MAX_AGENTS][8];  /* 1: negate action j of the agent in the env action
                                               vector (LegTransforms: fr / hr knee)          */
@@ -323,7 +324,16 @@ int ddrl_episodes_reset(ddrl_ctx* ctx);
  *                    nb_p = max(1, R_p / sgd_minibatch_size)
  *   kl_coeff[p]    : current KL coefficient
  * max_steps < 0 runs the whole schedule; >= 0 runs only the first max_steps minibatches.
- * All policies in the mask run concurrently (one persistent workgroup each). */
+ * All policies in the mask run concurrently (one persistent workgroup each).
+ * Row i of step (e, b) is shuffle[perm[e][b] * sgd_minibatch_size + i]; rows past
+ * nb * sgd_minibatch_size are left out; a train batch of fewer rows than one minibatch is refused.
+ * sgd_minibatch_size = 256 (fcnet models): the same schedule, statistics and rollback through
+ * the 256-row kernels, each of a branch's two workgroups on 128 rows.  It needs the row split
+ * (DDRL_UPDATE_SPLIT=1 is refused at ddrl_ctx_create).  Of the data-parallel entry points,
+ * ddrl_ppo_grad / ddrl_ppo_apply and ddrl_ppo_update_ddp work with rows_per_rank <= 128 (the
+ * gradient is scaled by 1 / 256, so the split over two or more ranks sums to the 256-row
+ * gradient); a whole 256-row minibatch per rank ("local" mode) and peer mode (ddrl_peer_attach)
+ * are refused. */
 int ddrl_ppo_update(ddrl_ctx* ctx, int pid_mask, const int32_t* const* shuffle_dev,
                     const int32_t* const* perm_dev, const float* kl_coeff, int max_steps);
 /* The same update resumed at minibatch step step0 of the schedule (step0 = e * nb + b), from the
@@ -379,7 +389,8 @@ int ddrl_ppo_update_ddp(ddrl_ctx* ctx, int pid, const int32_t* shuffle_dev, cons
  * quads, system-scope stores and loads; no collective, no per-step launch), then runs the same
  * clip + Adam:
  * both ranks' weights stay bit-identical to each other and to one fused launch over the union
- * batch.  fcnet models, row split on (the default), two ranks.
+ * batch.  fcnet models, row split on (the default), two ranks, sgd_minibatch_size 128 (a 256
+ * context is refused at ddrl_peer_attach).
  *   ddrl_peer_alloc: rank 0 allocates the outboxes (fine-grained device memory, cleared) and,
  *     with ipc_handle_out, exports them (DDRL_PEER_HANDLE_BYTES, hipIpcGetMemHandle);
  *   ddrl_peer_open: rank 1 maps rank 0's outboxes from that handle (another process);

@@ -6,9 +6,12 @@ row split (KSP = 2, default) and without it (DDRL_UPDATE_SPLIT=1: the 4-wave, sp
 instance), plus data-parallel gradient launches of <= 64 rows, and prints one JSON line with
 the violation counters of the staging / record / schedule / LDS / parameter indices.
 Exit status 0 only if every case passed its parity check and every counter is zero.
+--minibatch 256 runs the Local and A = 4 (TwoSides) parity cases of tests/test_gpu_minibatch.py
+instead: the 256-row kernels (ppo_ffn_mb256.hip), whose counters ddrl_diag_bounds adds in.
 
-    python tools/bounds_check.py
+    python tools/bounds_check.py [--minibatch 256]
 """
+import argparse
 import ctypes as C
 import json
 import os
@@ -33,11 +36,19 @@ def counters(lib, reset=False):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--minibatch", type=int, choices=(128, 256), default=128)
+    mb = ap.parse_args().minibatch
     lib = N.load(LIB)           # every later N.load() returns this library
     lib.ddrl_diag_bounds.argtypes = [C.POINTER(C.c_uint), C.c_int]
-    import test_gpu_parity as T
     cases = []
-    for split in ("2", "1"):
+    if mb == 256:
+        import test_gpu_minibatch as M
+        for args in M.UPDATE_CASES[:1] + [a for a in M.UPDATE_CASES if "TwoSides" in a[0]]:
+            cases.append((f"update{args[:4]} minibatch=256 split=2", lambda a=args: M.run_update_case(*a)))
+    else:
+        import test_gpu_parity as T
+    for split in ("2", "1") if mb == 128 else ():
         os.environ["DDRL_UPDATE_SPLIT"] = split
         for args in T.UPDATE_CASES:
             cases.append((f"update{args[:4]} split={split}", lambda a=args: T.test_ppo_update_parity(*a)))
