@@ -38,7 +38,9 @@ _VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 #    "256-row minibatches")
 SRC_FLAGS = {"ppo_ffn.hip": _ILP + _VGPR_MFMA, "ppo_ffn_peer.hip": _ILP + _VGPR_MFMA, "gnn.hip": _VGPR_MFMA,
              "ppo_ffn_atomic.hip": _VGPR_MFMA, "ppo_ffn_mb256.hip": _VGPR_MFMA,
-             "ppo_ffn_mb256_atomic.hip": _VGPR_MFMA}
+             "ppo_ffn_mb256_atomic.hip": _VGPR_MFMA,
+             # the device env plane matches the host plane's arithmetic: no a * b + c -> fma
+             "devenv.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

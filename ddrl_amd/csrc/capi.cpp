@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -143,8 +145,39 @@ struct ddrl_ctx {
   long long *ep_base = nullptr, *ep_word = nullptr;
   long long ep_cap = 0, ep_rows = -1;
   int ep_collected = 0;
+  // device env planes bound to this context (ddrl_devenv_*), and ddrl_rollout_devenv's graph:
+  // keyed by the env's id, its settings generation and the noise buffer
+  std::vector<ddrl_devenv*> devenvs;
+  hipGraphExec_t rgd_exec = nullptr;
+  uint64_t rgd_env = 0;
+  unsigned rgd_gen = 0;
+  const void* rgd_eps = nullptr;
   std::vector<void*> allocs;
 };
+
+// A device env plane (devenv.hip): the kernel arguments (state and output buffers in device
+// memory), the host copy of the target-velocity list and the scratch of state_get / state_set.
+struct ddrl_devenv {
+  ddrl_ctx* ctx = nullptr;       // null once the context is gone
+  uint64_t id = 0;               // unique per process (a graph key must not be an address that is reused)
+  unsigned gen = 0;              // bumped by every setting a captured launch has baked in
+  DevEnvArgs a{};
+  std::vector<double> tv_list;
+  double* tv_dev = nullptr;
+  size_t tv_cap = 0;
+  double* packed = nullptr;
+  std::vector<void*> allocs;
+};
+
+template <class T>
+static bool env_alloc(ddrl_devenv* e, T** p, size_t count) {
+  void* ptr = nullptr;
+  const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+  if (hipMalloc(&ptr, bytes) != hipSuccess) return false;
+  e->allocs.push_back(ptr);
+  *p = static_cast<T*>(ptr);
+  return hipMemset(ptr, 0, bytes) == hipSuccess;
+}
 
 template <class T>
 static int dalloc(ddrl_ctx* c, T** p, size_t count) {
@@ -359,6 +392,8 @@ int ddrl_ctx_destroy(ddrl_ctx* c) {
   if (c->comm) (void)ncclCommDestroy(c->comm);
   if (c->peer_ipc) (void)hipIpcCloseMemHandle(c->peer_ipc);
   if (c->rg_exec) (void)hipGraphExecDestroy(c->rg_exec);
+  if (c->rgd_exec) (void)hipGraphExecDestroy(c->rgd_exec);
+  for (ddrl_devenv* e : c->devenvs) e->ctx = nullptr;   // orphaned: only destroy is left to them
   if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
   for (void* p : c->allocs) (void)hipFree(p);
   delete c;
@@ -1207,6 +1242,250 @@ int ddrl_eval_hostenv(ddrl_ctx* c, ddrl_hostenv* env, const float* eps_dev, int 
   }
   // the pinned buffers are the caller's again only once the stream has consumed them
   if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("stream synchronize failed");
+  if (steps_run) *steps_run = t;
+  return rc ? -1 : 0;
+}
+
+// ---- device env plane (devenv.hip) --------------------------------------------------------
+static int chk_env(const ddrl_devenv* e) {
+  if (!e) return fail("null device env");
+  if (!e->ctx) return fail("device env: its context has been destroyed");
+  return 0;
+}
+#define CHK_ENV(e) \
+  if (chk_env(e)) return -1
+
+int ddrl_devenv_create(ddrl_ctx* c, uint64_t seed, float target_velocity, ddrl_devenv** out) {
+  CHK_CTX(c);
+  if (!out) return fail("ddrl_devenv_create: null output pointer");
+  const ddrl_cfg& g = c->cfg;
+  if (g.obs_full_dim != 43 && g.obs_full_dim != 44)
+    return fail("ddrl_devenv_create: the context's obs_full_dim must be 43 or 44");
+  if (g.obs_full_dim == 44 && !(target_velocity > 0.f))
+    return fail("ddrl_devenv_create: obs_full_dim 44 needs target_velocity > 0");
+  HIPCHK(hipSetDevice(c->device));   // the buffers live on the context's device
+  static std::atomic<uint64_t> next_id{0};
+  auto* e = new ddrl_devenv();
+  e->ctx = c;
+  e->id = ++next_id;
+  const size_t N = g.n_envs;
+  DevEnvArgs& a = e->a;
+  a.N = g.n_envs; a.D = g.obs_full_dim; a.time_limit = 1000; a.n_tv = 1; a.seed = seed;
+  e->tv_cap = 16;
+  e->tv_list.assign(1, (double)target_velocity);
+  // the create-time velocity until the first reset draws one, as the host plane
+  const std::vector<double> tv0(N, (double)target_velocity);
+  const bool ok = env_alloc(e, &a.st, (size_t)DDRL_DEVENV_FIELDS * N) && env_alloc(e, &a.steps, N) && env_alloc(e, &a.episode, N) &&
+                  env_alloc(e, &e->tv_dev, e->tv_cap) && env_alloc(e, &a.obs, N * a.D) && env_alloc(e, &a.fw, N) && env_alloc(e, &a.cfrc, N * 84) &&
+                  env_alloc(e, &a.kin, N * 9) && env_alloc(e, &a.done, N) && env_alloc(e, &e->packed, N * DDRL_ENV_STATE_DOUBLES) &&
+                  hipMemcpy(a.st + 38 * N, tv0.data(), N * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(e->tv_dev, e->tv_list.data(), 8, hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    for (void* p : e->allocs) (void)hipFree(p);
+    delete e;
+    return fail("ddrl_devenv_create: device buffer allocation failed");
+  }
+  a.tv_list = e->tv_dev;
+  c->devenvs.push_back(e);
+  *out = e;
+  return 0;
+}
+
+int ddrl_devenv_destroy(ddrl_devenv* e) {
+  if (!e) return 0;
+  if (ddrl_ctx* c = e->ctx) {
+    (void)hipStreamSynchronize(c->stream);   // nothing in flight touches the buffers
+    c->devenvs.erase(std::remove(c->devenvs.begin(), c->devenvs.end(), e), c->devenvs.end());
+  }
+  for (void* p : e->allocs) (void)hipFree(p);
+  delete e;
+  return 0;
+}
+
+int ddrl_devenv_buffers(ddrl_devenv* e, float** obs, float** fw, float** cfrc, float** kin, uint8_t** done) {
+  CHK_ENV(e);
+  if (obs) *obs = e->a.obs;
+  if (fw) *fw = e->a.fw;
+  if (cfrc) *cfrc = e->a.cfrc;
+  if (kin) *kin = e->a.kin;
+  if (done) *done = e->a.done;
+  return 0;
+}
+
+static int devenv_reset(ddrl_devenv* e, int mode) {
+  CHK_ENV(e);
+  launch_devenv_reset(e->ctx->stream, e->a, mode);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+int ddrl_devenv_reset(ddrl_devenv* e) { return devenv_reset(e, DEVENV_RESET_ALL); }
+int ddrl_devenv_reset_episodes(ddrl_devenv* e) { return devenv_reset(e, DEVENV_RESET_EPISODES); }
+int ddrl_devenv_reset_state(ddrl_devenv* e) { return devenv_reset(e, DEVENV_RESET_STATE); }
+
+int ddrl_devenv_set_time_limit(ddrl_devenv* e, int steps) {
+  CHK_ENV(e);
+  if (steps < 1) return fail("ddrl_devenv_set_time_limit: steps >= 1");
+  e->a.time_limit = steps;
+  ++e->gen;
+  return 0;
+}
+
+int ddrl_devenv_set_target_velocities(ddrl_devenv* e, const float* list, int n) {
+  CHK_ENV(e);
+  if (!list || n < 1) return fail("ddrl_devenv_set_target_velocities: a list of n >= 1 values");
+  for (int i = 0; i < n; ++i) {
+    if (!std::isfinite(list[i])) return fail("ddrl_devenv_set_target_velocities: target velocities must be finite");
+    if (e->a.D > 43 && !(list[i] > 0.f))
+      return fail("ddrl_devenv_set_target_velocities: obs_dim 44 needs target velocities > 0 "
+                  "(the TVel reward divides by it)");
+  }
+  // launches in flight still read the old list
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));
+  if ((size_t)n > e->tv_cap) {
+    double* p = nullptr;
+    HIPCHK(hipMalloc((void**)&p, (size_t)n * 8));
+    e->allocs.push_back(p);   // the smaller list is freed with the env
+    e->tv_dev = p;
+    e->tv_cap = n;
+  }
+  e->tv_list.assign(list, list + n);
+  HIPCHK(hipMemcpy(e->tv_dev, e->tv_list.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  e->a.tv_list = e->tv_dev;
+  e->a.n_tv = n;
+  ++e->gen;
+  return 0;
+}
+
+int ddrl_devenv_target_velocities(ddrl_devenv* e, float* out, int n) {
+  CHK_ENV(e);
+  if (!out || n != e->a.N) return fail("ddrl_devenv_target_velocities: out holds n_envs floats");
+  std::vector<double> tv(n);
+  HIPCHK(hipMemcpyAsync(tv.data(), e->a.st + (size_t)38 * n, (size_t)n * 8, hipMemcpyDeviceToHost, e->ctx->stream));
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));
+  for (int i = 0; i < n; ++i) out[i] = (float)tv[i];
+  return 0;
+}
+
+int ddrl_devenv_step(ddrl_devenv* e, const float* actions) {
+  CHK_ENV(e);
+  if (!actions) return fail("ddrl_devenv_step: null actions buffer");
+  launch_devenv_step(e->ctx->stream, e->a, actions);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ddrl_devenv_state_get(ddrl_devenv* e, double* host, size_t n) {
+  CHK_ENV(e);
+  if (!host || n != (size_t)e->a.N * DDRL_ENV_STATE_DOUBLES)
+    return fail("ddrl_devenv_state_get: n == n_envs * DDRL_ENV_STATE_DOUBLES doubles");
+  launch_devenv_pack(e->ctx->stream, e->a, e->packed, 0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(host, e->packed, n * 8, hipMemcpyDeviceToHost, e->ctx->stream));
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));
+  return 0;
+}
+
+int ddrl_devenv_state_set(ddrl_devenv* e, const double* host, size_t n) {
+  CHK_ENV(e);
+  if (!host || n != (size_t)e->a.N * DDRL_ENV_STATE_DOUBLES)
+    return fail("ddrl_devenv_state_set: n == n_envs * DDRL_ENV_STATE_DOUBLES doubles");
+  for (int i = 0; i < e->a.N; ++i)
+    if (!envdyn::packed_counts_ok(host + (size_t)i * DDRL_ENV_STATE_DOUBLES))
+      return fail("ddrl_devenv_state_set: steps and episode must be non-negative integers");
+  HIPCHK(hipMemcpyAsync(e->packed, host, n * 8, hipMemcpyHostToDevice, e->ctx->stream));
+  launch_devenv_pack(e->ctx->stream, e->a, e->packed, 1);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));   // `host` is read until here
+  return 0;
+}
+
+static int chk_env_of(const ddrl_ctx* c, const ddrl_devenv* e) {
+  if (chk_env(e)) return -1;
+  if (e->ctx != c) return fail("device env belongs to another context");
+  return 0;
+}
+
+// act(t) -> env step -> reward(t) -> observe for every t, then the bootstrap: one linear chain
+static int devenv_launches(ddrl_ctx* c, ddrl_devenv* e, const float* eps) {
+  const ddrl_cfg& g = c->cfg;
+  const size_t eps_step = (size_t)g.n_envs * g.n_agents * g.act_dim;
+  for (int t = 0; t < g.frag_len; ++t) {
+    if (ddrl_act(c, t, eps + (size_t)t * eps_step, c->h_act) || ddrl_devenv_step(e, c->h_act) ||
+        ddrl_reward(c, t, e->a.fw, e->a.cfrc, c->h_act, e->a.done) || ddrl_observe(c, e->a.obs))
+      return -1;
+  }
+  return ddrl_bootstrap(c);
+}
+
+int ddrl_rollout_devenv(ddrl_ctx* c, ddrl_devenv* e, const float* eps_dev, int reset) {
+  CHK_CTX(c);
+  if (chk_env_of(c, e)) return -1;
+  if (!eps_dev) return fail("null noise buffer");
+  if (reset && (ddrl_devenv_reset(e) || ddrl_observe(c, e->a.obs))) return -1;
+  if (!c->rollout_graph) return devenv_launches(c, e, eps_dev);
+  if (!c->rgd_exec || c->rgd_env != e->id || c->rgd_gen != e->gen || c->rgd_eps != eps_dev) {
+    if (c->rgd_exec) {
+      HIPCHK(hipGraphExecDestroy(c->rgd_exec));
+      c->rgd_exec = nullptr;
+    }
+    // captured on a private stream (a capture records, it does not run), launched on the caller's
+    if (!c->cap_stream) HIPCHK(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
+    const hipStream_t user = c->stream;
+    c->stream = c->cap_stream;
+    hipError_t er = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
+    if (er != hipSuccess) {
+      c->stream = user;
+      return fail(std::string("rollout graph capture: ") + hipGetErrorString(er));
+    }
+    const int rc = devenv_launches(c, e, eps_dev);
+    hipGraph_t graph = nullptr;
+    er = hipStreamEndCapture(c->stream, &graph);
+    c->stream = user;
+    if (rc) {
+      if (graph) (void)hipGraphDestroy(graph);
+      return -1;
+    }
+    if (er != hipSuccess) return fail(std::string("rollout graph capture: ") + hipGetErrorString(er));
+    const hipError_t ei = hipGraphInstantiate(&c->rgd_exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ei != hipSuccess) {
+      c->rgd_exec = nullptr;
+      return fail(std::string("rollout graph instantiate: ") + hipGetErrorString(ei));
+    }
+    c->rgd_env = e->id; c->rgd_gen = e->gen; c->rgd_eps = eps_dev;
+  }
+  HIPCHK(hipGraphLaunch(c->rgd_exec, c->stream));
+  // what the replayed calls would have noted on the host
+  c->ep_collected = 0;
+  c->ev_normc_ok = 0;
+  c->sens_act_ok = 0;
+  return 0;
+}
+
+int ddrl_eval_devenv(ddrl_ctx* c, ddrl_devenv* e, const float* eps_dev, int eps_steps, int max_steps, int poll_every,
+                     int* steps_run) {
+  CHK_EVAL(c);
+  if (chk_env_of(c, e)) return -1;
+  const ddrl_cfg& g = c->cfg;
+  if (max_steps < 1 || poll_every < 1) return fail("evaluation: max_steps and poll_every must be >= 1");
+  if (eps_dev && eps_steps < 1) return fail("evaluation: eps_steps must be >= 1 with a noise buffer");
+  const size_t N = g.n_envs;
+  const size_t eps_step = N * g.n_agents * g.act_dim;
+  const int limit = eps_dev ? std::min(max_steps, eps_steps) : max_steps;
+  int rc = ddrl_devenv_reset_episodes(e);
+  int t = 0;
+  for (; t < limit && !rc;) {
+    rc = ddrl_eval_act(c, e->a.obs, eps_dev ? eps_dev + (size_t)t * eps_step : nullptr, c->h_act, nullptr);
+    if (!rc && c->sens_on) rc = ddrl_eval_sens(c, e->a.obs, nullptr);
+    rc = rc || ddrl_devenv_step(e, c->h_act) || ddrl_eval_step(c, e->a.fw, e->a.cfrc, c->h_act, e->a.kin, e->a.done);
+    if (rc) break;
+    ++t;
+    if (t % poll_every == 0) {
+      int64_t eps_done = 0, fin = 0;
+      rc = ddrl_eval_progress(c, &eps_done, &fin);
+      if (!rc && fin == (int64_t)N) break;
+    }
+  }
   if (steps_run) *steps_run = t;
   return rc ? -1 : 0;
 }

@@ -82,152 +82,28 @@ void Pool::parallel_for(int n, const std::function<void(int, int)>& fn) {
   job_ = nullptr;
 }
 
-// counter-based generator: uniform in [-1, 1) from (seed, env, episode, draw)
-static double hash_uniform(uint64_t seed, uint64_t env, uint64_t episode, uint64_t k) {
-  uint64_t z = seed ^ (env * 0x9E3779B97F4A7C15ull) ^ (episode * 0xBF58476D1CE4E5B9ull) ^ (k * 0x94D049BB133111EBull);
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-}
-
 }  // namespace hostenv
 
 using hostenv::EnvState;
 
-namespace {
-constexpr double kH = 0.01;           // integration step; frame_skip 5 -> 0.05 s per env step
-constexpr int kFrameSkip = 5;
-constexpr double kDt = kH * kFrameSkip;
-constexpr double kQ0[8] = {0.0, 1.0, 0.0, -1.0, 0.0, -1.0, 0.0, 1.0};   // rest pose (knees bent)
-constexpr double kGear = 30.0, kSpring = 8.0, kDamp = 1.5, kLimit = 1.4;
-constexpr double kShin = 0.7, kHipOff = 0.08, kGround = 400.0, kGroundDamp = 8.0;
-constexpr uint64_t kTvDraw = 1u << 20;   // counter index of the target-velocity draw (pose draws use 0..16)
-}  // namespace
-
+// The dynamics are envdyn.h's, shared with the device plane (devenv.hip).
 void ddrl_hostenv::reset_env(int e, bool draw_tv) {
-  EnvState& s = st[e];
-  const uint32_t ep = s.episode + 1;
-  const double tv = s.tv;
-  std::memset(&s, 0, sizeof(s));
-  s.episode = ep;
-  s.tv = tv;
-  if (draw_tv) {
-    // random.choice(target_velocity_list): every list position equally likely (a repeated value
-    // counts once per position); draw index kTvDraw of the episode's counter stream
-    const double u = 0.5 * (hostenv::hash_uniform(seed, e, ep, kTvDraw) + 1.0);   // [0, 1)
-    const size_t n = tv_list.size();
-    s.tv = tv_list[std::min(n - 1, (size_t)(u * (double)n))];
-  }
-  int k = 0;
-  s.z = 0.57 + 0.01 * hostenv::hash_uniform(seed, e, ep, k++);
-  for (int j = 0; j < 8; ++j) {
-    s.q[j] = kQ0[j] + 0.1 * hostenv::hash_uniform(seed, e, ep, k++);
-    s.qd[j] = 0.1 * hostenv::hash_uniform(seed, e, ep, k++);
-  }
+  envdyn::reset_env(st[e], seed, e, draw_tv, tv_list.data(), (int)tv_list.size());
 }
 
-void ddrl_hostenv::write_obs(int e, const double* ctrl) {
-  const EnvState& s = st[e];
-  float* o = obs + (size_t)e * D;
-  // quaternion (w, x, y, z) of roll about x then pitch about y
-  const double cr = std::cos(0.5 * s.roll), sr = std::sin(0.5 * s.roll);
-  const double cp = std::cos(0.5 * s.pitch), sp = std::sin(0.5 * s.pitch);
-  const double qpos[13] = {s.z, cr * cp, sr * cp, cr * sp, -sr * sp, s.q[0], s.q[1], s.q[2], s.q[3],
-                           s.q[4], s.q[5], s.q[6], s.q[7]};
-  const double qvel[14] = {s.vx, s.vy, s.vz, s.wroll, s.wpitch, 0.0, s.qd[0], s.qd[1], s.qd[2], s.qd[3],
-                           s.qd[4], s.qd[5], s.qd[6], s.qd[7]};
-  int i = 0;
-  for (double v : qpos) o[i++] = (float)v;
-  for (double v : qvel) o[i++] = (float)v;
-  for (int j = 0; j < 8; ++j) o[i++] = (float)s.qfrc[j];
-  for (int j = 0; j < 8; ++j) o[i++] = (float)(ctrl ? ctrl[j] : 0.0);
-  if (D > 43) o[i++] = (float)s.tv;
-}
+void ddrl_hostenv::write_obs(int e, const double* ctrl) { envdyn::write_obs(st[e], obs + (size_t)e * D, D, ctrl); }
 
 void ddrl_hostenv::step_env(int e, const float* a8) {
-  EnvState& s = st[e];
-  double a[8];
-  for (int j = 0; j < 8; ++j) a[j] = std::min(1.0, std::max(-1.0, (double)a8[j]));
-  const double x0 = s.x;
-  for (int f = 0; f < kFrameSkip; ++f) {
-    double thrust = 0.0, lift = 0.0, troll = 0.0, tpitch = 0.0;
-    for (int leg = 0; leg < 4; ++leg) {
-      const int hip = 2 * leg, knee = hip + 1;
-      // foot height below the hip: shin along the knee angle, hip swing lifts it a little
-      const double fz = s.z - kShin * std::cos(s.q[knee]) * std::cos(s.q[hip]) + kHipOff * std::fabs(std::sin(s.q[hip]));
-      double force = 0.0;
-      if (fz < 0.0) force = std::max(0.0, -kGround * fz - kGroundDamp * s.vz);
-      s.foot[leg] = force;
-      // a stance foot pushes the torso by the hip's backward swing
-      thrust += force * 0.05 * (-s.qd[hip]) * std::cos(s.q[hip]);
-      lift += force;
-      const double side = (leg == 0 || leg == 1) ? 1.0 : -1.0;    // FL, HL left; HR, FR right
-      const double front = (leg == 0 || leg == 3) ? 1.0 : -1.0;   // FL, FR front
-      troll += side * force;
-      tpitch += front * force;
-    }
-    for (int j = 0; j < 8; ++j) {
-      const double tau = kGear * a[j];
-      double qdd = tau - kSpring * (s.q[j] - kQ0[j]) - kDamp * s.qd[j];
-      s.qd[j] += kH * qdd;
-      s.q[j] += kH * s.qd[j];
-      double constraint = 0.0;
-      if (s.q[j] > kLimit || s.q[j] < -kLimit) {   // joint limit: stop and report the reaction
-        const double lim = s.q[j] > 0 ? kLimit : -kLimit;
-        constraint = -(s.q[j] - lim) / (kH * kH);
-        s.q[j] = lim;
-        s.qd[j] = 0.0;
-      }
-      s.qfrc[j] = tau + std::max(-100.0, std::min(100.0, constraint));
-    }
-    s.vx += kH * (thrust - 0.8 * s.vx);
-    s.vy += kH * (-0.8 * s.vy + 0.02 * troll * std::sin(s.roll));
-    s.vz += kH * (lift / 8.0 - 9.81 - 1.0 * s.vz);
-    s.wroll += kH * (0.02 * troll - 4.0 * s.roll - 1.5 * s.wroll);
-    s.wpitch += kH * (0.02 * tpitch - 4.0 * s.pitch - 1.5 * s.wpitch);
-    s.x += kH * s.vx;
-    s.y += kH * s.vy;
-    s.z += kH * s.vz;
-    s.roll += kH * s.wroll;
-    s.pitch += kH * s.wpitch;
-  }
-  ++s.steps;
-  // forward reward of the step (quantruped_v3.py:163-179): the torso's x velocity; the TVel
-  // envs reward reaching the target velocity instead (QuAntrupedTVelEnv.compute_forward_reward,
-  // quantruped_v3.py:391-392)
-  const double vx = (s.x - x0) / kDt;
-  if (D > 43) {
-    const double tv = s.tv;
-    fw[e] = (float)((1.0 + 1.0 / tv) * (1.0 / (std::fabs(vx - tv) + 1.0) - 1.0 / (tv + 1.0)));
-  } else {
-    fw[e] = (float)vx;
-  }
-  // cfrc_ext [14][6]: {floor, torso, then hip / leg / foot of FL, HL, HR, FR}; rotational then
-  // linear part, the contact force on the foot bodies
-  float* cf = cfrc + (size_t)e * 14 * 6;
-  std::fill(cf, cf + 14 * 6, 0.f);
-  for (int leg = 0; leg < 4; ++leg) {
-    float* foot = cf + (4 + 3 * leg) * 6;
-    const double f = s.foot[leg];
-    foot[0] = (float)(0.01 * f * std::sin(s.q[2 * leg]));
-    foot[3] = (float)(0.1 * f * std::sin(s.q[2 * leg]));
-    foot[5] = (float)f;
-    cf[1 * 6 + 5] += (float)(0.05 * f);
-  }
-  float* kn = kin + (size_t)e * 9;
-  kn[0] = (float)(s.x - x0);
-  for (int j = 0; j < 8; ++j) kn[1 + j] = (float)s.qd[j];
-  const bool unhealthy = !(s.z > 0.1 && s.z < 1.5) || !std::isfinite(s.z);
-  const bool d = unhealthy || s.steps >= time_limit;
-  done[e] = d ? 1 : 0;
-  if (d) {
-    reset_env(e);
-    write_obs(e, nullptr);
-  } else {
-    write_obs(e, a);
-  }
+  envdyn::step_env(st[e], a8, obs + (size_t)e * D, fw + e, cfrc + (size_t)e * 14 * 6, kin + (size_t)e * 9, done + e, D,
+                   time_limit, seed, e, tv_list.data(), (int)tv_list.size());
+}
+
+void ddrl_hostenv::state_get(double* out) const {
+  for (int e = 0; e < N; ++e) envdyn::pack_state(st[e], out + (size_t)e * envdyn::kStateDoubles);
+}
+
+void ddrl_hostenv::state_set(const double* in) {
+  for (int e = 0; e < N; ++e) envdyn::unpack_state(in + (size_t)e * envdyn::kStateDoubles, st[e]);
 }
 
 void ddrl_hostenv::reset_all() {
@@ -236,7 +112,7 @@ void ddrl_hostenv::reset_all() {
       st[e].episode = 0;
       reset_env(e);
       // staggered episode phases, like a long-running sampler (the synthetic rollouts too)
-      st[e].steps = (int)(((uint64_t)e * 2654435761ull + seed) % time_limit);
+      st[e].steps = envdyn::stagger_steps(seed, e, time_limit);
       write_obs(e, nullptr);
       done[e] = 0;
     }
@@ -414,5 +290,29 @@ extern "C" int ddrl_hostenv_reset_episodes(ddrl_hostenv* h) {
     return -1;
   }
   h->reset_episodes();
+  return 0;
+}
+
+extern "C" int ddrl_hostenv_state_get(ddrl_hostenv* h, double* host, size_t n) {
+  if (!h || !host || n != (size_t)h->N * envdyn::kStateDoubles) {
+    g_henv_err = "ddrl_hostenv_state_get: a host env and n == n_envs * DDRL_ENV_STATE_DOUBLES doubles";
+    return -1;
+  }
+  h->state_get(host);
+  return 0;
+}
+
+extern "C" int ddrl_hostenv_state_set(ddrl_hostenv* h, const double* host, size_t n) {
+  if (!h || !host || n != (size_t)h->N * envdyn::kStateDoubles) {
+    g_henv_err = "ddrl_hostenv_state_set: a host env and n == n_envs * DDRL_ENV_STATE_DOUBLES doubles";
+    return -1;
+  }
+  for (int e = 0; e < h->N; ++e) {
+    if (!envdyn::packed_counts_ok(host + (size_t)e * envdyn::kStateDoubles)) {
+      g_henv_err = "ddrl_hostenv_state_set: steps and episode must be non-negative integers";
+      return -1;
+    }
+  }
+  h->state_set(host);
   return 0;
 }

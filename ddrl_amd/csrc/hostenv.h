@@ -24,18 +24,11 @@
 #include <thread>
 #include <vector>
 
+#include "envdyn.h"
+
 namespace hostenv {
 
-struct EnvState {
-  double x, y, z, vx, vy, vz;       // torso position / velocity
-  double roll, pitch, wroll, wpitch;
-  double q[8], qd[8];               // joints: [FL hip, FL knee, HL hip, HL knee, HR hip, HR knee, FR hip, FR knee]
-  double qfrc[8];                   // last actuator + constraint force per joint
-  double foot[4];                   // last contact force per foot
-  int steps;                        // steps in the current episode
-  uint32_t episode;
-  double tv;                        // target velocity of the current episode (TVel envs)
-};
+using envdyn::EnvState;   // the env state and its dynamics are shared with the device plane (envdyn.h)
 
 // Persistent worker threads; parallel_for splits [0, n) in contiguous chunks, the caller
 // takes part, and returns when every chunk is done.
@@ -80,6 +73,9 @@ struct ddrl_hostenv {
   void reset_env(int e, bool draw_tv = true);
   void write_obs(int e, const double* ctrl);
   void step_env(int e, const float* a8);
+  // the packed state of every env (envdyn::kStateDoubles doubles each, envdyn::pack_state)
+  void state_get(double* out) const;
+  void state_set(const double* in);
   void reset_all();
   // update_environment_after_epoch (adaptor :97-122): every env's physical state and episode
   // step count restart (gym env.reset()), the target velocity stays (only the adaptor's own

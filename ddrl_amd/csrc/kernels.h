@@ -192,6 +192,27 @@ struct EpArgs {
 void launch_ep_count_scan(hipStream_t s, const EpArgs& a);   // cnt, base, total
 void launch_ep_walk(hipStream_t s, const EpArgs& a);         // table rows + the in-flight state
 
+// ---- device env plane (devenv.hip; the dynamics are envdyn.h's) ----
+// The env state is a struct of arrays: st[f][N], f = the first 38 entries of the packed layout
+// (torso 10, q 8, qd 8, qfrc 8, foot 4) and the target velocity as field 38; steps and episode
+// as integer arrays.
+#define DDRL_DEVENV_FIELDS 39
+struct DevEnvArgs {
+  int N, D, time_limit, n_tv;
+  unsigned long long seed;
+  double* st;                // [DDRL_DEVENV_FIELDS][N]
+  int* steps;                // [N]
+  unsigned* episode;         // [N]
+  const double* tv_list;     // [n_tv]
+  float *obs, *fw, *cfrc, *kin;   // [N][D], [N], [N][14][6], [N][9]
+  uint8_t* done;             // [N]
+};
+enum { DEVENV_RESET_ALL = 0, DEVENV_RESET_EPISODES = 1, DEVENV_RESET_STATE = 2 };
+void launch_devenv_step(hipStream_t s, const DevEnvArgs& a, const float* actions);   // four lanes per env
+void launch_devenv_reset(hipStream_t s, const DevEnvArgs& a, int mode);
+// packed[N][41] (DDRL_ENV_STATE_DOUBLES) <- state, or state <- packed when unpack
+void launch_devenv_pack(hipStream_t s, const DevEnvArgs& a, double* packed, int unpack);
+
 // ---- PPO update (fused persistent minibatch loop) ----
 struct UpdateArgs {
   const float* rec; RecLayout lay;

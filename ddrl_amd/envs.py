@@ -72,3 +72,31 @@ class HostVecEnv:
 
     def close(self):
         self.env.close()
+
+
+class DeviceVecEnv:
+    """The device env plane (ddrl_amd.native.DevEnv: the same stand-in stepped by a HIP kernel on
+    the rollout context's stream) as a trainer backend.  step() is one launch; what it returns are
+    the plane's own device buffers, rewritten in place by the next step -- no host copy, no host
+    thread, no synchronization."""
+
+    def __init__(self, ctx, seed=0, target_velocity=0.0):
+        from .native import DevEnv
+        self.env = DevEnv(ctx, seed, target_velocity)
+
+    def reset(self):
+        return self.env.reset()
+
+    def step(self, actions):
+        self.env.step(actions)
+        return self.env.obs, self.env.fw, self.env.cfrc, self.env.done
+
+    def update_environment_after_epoch(self, timesteps_total):
+        self.env.reset_state()
+
+    @property
+    def target_velocities(self):
+        return self.env.target_velocities
+
+    def close(self):
+        self.env.close()

@@ -129,6 +129,23 @@ _SIGS = {
     "ddrl_hostenv_kin": ([VP, C.POINTER(VP)], C.c_int),
     "ddrl_hostenv_set_time_limit": ([VP, C.c_int], C.c_int),
     "ddrl_hostenv_reset_episodes": ([VP], C.c_int),
+    "ddrl_hostenv_state_get": ([VP, VP, C.c_size_t], C.c_int),
+    "ddrl_hostenv_state_set": ([VP, VP, C.c_size_t], C.c_int),
+    "ddrl_devenv_create": ([VP, C.c_uint64, f32, C.POINTER(VP)], C.c_int),
+    "ddrl_devenv_destroy": ([VP], C.c_int),
+    "ddrl_devenv_buffers": ([VP, C.POINTER(VP), C.POINTER(VP), C.POINTER(VP), C.POINTER(VP), C.POINTER(VP)],
+                            C.c_int),
+    "ddrl_devenv_reset": ([VP], C.c_int),
+    "ddrl_devenv_reset_episodes": ([VP], C.c_int),
+    "ddrl_devenv_reset_state": ([VP], C.c_int),
+    "ddrl_devenv_set_time_limit": ([VP, C.c_int], C.c_int),
+    "ddrl_devenv_set_target_velocities": ([VP, C.POINTER(C.c_float), C.c_int], C.c_int),
+    "ddrl_devenv_target_velocities": ([VP, C.POINTER(C.c_float), C.c_int], C.c_int),
+    "ddrl_devenv_step": ([VP, VP], C.c_int),
+    "ddrl_devenv_state_get": ([VP, VP, C.c_size_t], C.c_int),
+    "ddrl_devenv_state_set": ([VP, VP, C.c_size_t], C.c_int),
+    "ddrl_rollout_devenv": ([VP, VP, VP, C.c_int], C.c_int),
+    "ddrl_eval_devenv": ([VP, VP, VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
     "ddrl_eval_begin": ([VP, C.POINTER(DdrlEvalCfg)], C.c_int),
     "ddrl_eval_act": ([VP, VP, VP, VP, C.POINTER(VP)], C.c_int),
     "ddrl_eval_step": ([VP, VP, VP, VP, VP, VP], C.c_int),
@@ -161,6 +178,10 @@ def header_symbols(path=HEADER):
 ABI_VERSION = 4   # DDRL_ABI_VERSION of include/ddrl_hip.h (ddrl_cfg layout, record layout)
 COMM_ID_BYTES = 128   # DDRL_COMM_ID_BYTES (sizeof ncclUniqueId)
 PEER_HANDLE_BYTES = 64   # DDRL_PEER_HANDLE_BYTES (sizeof hipIpcMemHandle_t)
+# DDRL_ENV_STATE_DOUBLES: the packed per-env state of both env planes, and its columns
+ENV_STATE_DOUBLES = 41
+ENV_STATE_COLUMNS = {"torso": slice(0, 10), "q": slice(10, 18), "qd": slice(18, 26), "qfrc": slice(26, 34),
+                     "foot": slice(34, 38), "steps": 38, "episode": 39, "tv": 40}
 
 
 def comm_unique_id():
@@ -547,6 +568,19 @@ class Context:
                                        C.byref(n)))
         return int(n.value)
 
+    def rollout_devenv(self, env, eps_dev, reset=False):
+        """A fragment with the envs stepped on the device (DevEnv): one in-order chain of launches
+        on the context's stream (a replayed HIP graph), no copies and no host wait."""
+        _ck(self.lib.ddrl_rollout_devenv(self.h, env.h, _ptr(eps_dev), 1 if reset else 0))
+
+    def eval_devenv(self, env, eps_dev=None, eps_steps=0, max_steps=1000, poll_every=25):
+        """The whole evaluation over a DevEnv, loop in C++, the env's buffers read in place;
+        returns the env steps taken."""
+        n = C.c_int()
+        _ck(self.lib.ddrl_eval_devenv(self.h, env.h, _ptr(eps_dev), int(eps_steps), int(max_steps), int(poll_every),
+                                      C.byref(n)))
+        return int(n.value)
+
     # ---- input sensitivity of the evaluated policies (between eval_begin and eval_end) ----
     def eval_sens_begin(self, steps):
         """steps: per policy the perturbation h_f of each env-normalized input, obs_dim[p] finite
@@ -653,6 +687,19 @@ class HostEnv:
         self._ck(self.lib.ddrl_hostenv_reset_episodes(self.h))
         return self.obs.copy()
 
+    def state(self):
+        """The packed fp64 state of every env, [N, ENV_STATE_DOUBLES] (ENV_STATE_COLUMNS)."""
+        self._live()
+        a = np.empty((self.n, ENV_STATE_DOUBLES), np.float64)
+        self._ck(self.lib.ddrl_hostenv_state_get(self.h, a.ctypes.data, a.size))
+        return a
+
+    def set_state(self, state):
+        """Replace every env's state (the output buffers keep their contents until the next step)."""
+        self._live()
+        a = np.ascontiguousarray(state, np.float64)
+        self._ck(self.lib.ddrl_hostenv_state_set(self.h, a.ctypes.data, a.size))
+
     @property
     def target_velocities(self):
         """Each env's current target velocity (the draw of its current episode)."""
@@ -668,6 +715,113 @@ class HostEnv:
         if getattr(self, "h", None):
             self.obs = self.act = self.fw = self.cfrc = self.done = self.kin = None
             self.lib.ddrl_hostenv_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DevEnv:
+    """The device env plane (devenv.hip): the context's N stand-in envs stepped by a HIP kernel on
+    the context's stream.  obs [N][D], fw [N], cfrc [N][14][6], kin [N][9] and done [N] are torch
+    CUDA tensors over the library's memory (no copy); a step rewrites them in place."""
+
+    def __init__(self, ctx: Context, seed=0, target_velocity=0.0):
+        """target_velocity: one value, or the list every env draws its episode's velocity from."""
+        import torch
+        self.lib = load()
+        self.ctx = ctx   # keeps the context alive; close() the env before the context
+        h = VP()
+        tvs = [float(v) for v in (target_velocity if np.ndim(target_velocity) else [target_velocity])]
+        _ck(self.lib.ddrl_devenv_create(ctx.h, seed, tvs[0], C.byref(h)))
+        self.h, self.n, self.obs_dim = h, ctx.cfg.n_envs, ctx.cfg.obs_full_dim
+        if len(tvs) > 1:
+            try:
+                self.set_target_velocities(tvs)
+            except DdrlError:
+                self.lib.ddrl_devenv_destroy(h)
+                self.h = None
+                raise
+        ptrs = [VP() for _ in range(5)]
+        _ck(self.lib.ddrl_devenv_buffers(h, *[C.byref(p) for p in ptrs]))
+        dev = torch.device("cuda", ctx.device)
+
+        def view(p, typestr, shape):
+            class _View:
+                __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (p.value, False),
+                                            "version": 3, "strides": None}
+            return torch.as_tensor(_View(), device=dev)
+        n, D = self.n, self.obs_dim
+        self.obs = view(ptrs[0], "<f4", (n, D))
+        self.fw = view(ptrs[1], "<f4", (n,))
+        self.cfrc = view(ptrs[2], "<f4", (n, 14, 6))
+        self.kin = view(ptrs[3], "<f4", (n, 9))
+        self.done = view(ptrs[4], "|u1", (n,))
+
+    def _live(self):
+        if not getattr(self, "h", None):
+            raise DdrlError("device env plane is closed")
+
+    def reset(self):
+        """Reset every env (staggered episode phases); returns self.obs, the live buffer."""
+        self._live()
+        _ck(self.lib.ddrl_devenv_reset(self.h))
+        return self.obs
+
+    def reset_episodes(self):
+        """Every env starts a fresh episode at step 0; returns self.obs."""
+        self._live()
+        _ck(self.lib.ddrl_devenv_reset_episodes(self.h))
+        return self.obs
+
+    def reset_state(self):
+        """update_environment_after_epoch's env.reset(): state and TimeLimit count restart; target
+        velocities, done flags and self.obs stay."""
+        self._live()
+        _ck(self.lib.ddrl_devenv_reset_state(self.h))
+
+    def set_time_limit(self, steps):
+        self._live()
+        _ck(self.lib.ddrl_devenv_set_time_limit(self.h, int(steps)))
+
+    def set_target_velocities(self, tvs):
+        self._live()
+        tvs = [float(v) for v in tvs]
+        _ck(self.lib.ddrl_devenv_set_target_velocities(self.h, (C.c_float * len(tvs))(*tvs), len(tvs)))
+
+    @property
+    def target_velocities(self):
+        """Each env's current target velocity; synchronizes."""
+        self._live()
+        out = np.zeros(self.n, np.float32)
+        _ck(self.lib.ddrl_devenv_target_velocities(self.h, out.ctypes.data_as(C.POINTER(C.c_float)), self.n))
+        return out
+
+    def step(self, actions_dev):
+        """One launch on the context's stream: actions_dev [N][8] float32 in device memory."""
+        self._live()
+        _ck(self.lib.ddrl_devenv_step(self.h, _ptr(actions_dev)))
+
+    def state(self):
+        """The packed fp64 state of every env, [N, ENV_STATE_DOUBLES]; synchronizes."""
+        self._live()
+        a = np.empty((self.n, ENV_STATE_DOUBLES), np.float64)
+        _ck(self.lib.ddrl_devenv_state_get(self.h, a.ctypes.data, a.size))
+        return a
+
+    def set_state(self, state):
+        self._live()
+        a = np.ascontiguousarray(state, np.float64)
+        _ck(self.lib.ddrl_devenv_state_set(self.h, a.ctypes.data, a.size))
+
+    def close(self):
+        """Free the device buffers; the tensors over them are dropped first."""
+        if getattr(self, "h", None):
+            self.obs = self.fw = self.cfrc = self.kin = self.done = None
+            self.lib.ddrl_devenv_destroy(self.h)
             self.h = None
 
     def __del__(self):

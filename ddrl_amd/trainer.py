@@ -105,6 +105,11 @@ class PPOTrainer:
             env_backend = HostVecEnv(self.n_envs, self.cfg.obs_full_dim, self.device, seed=env_seed,
                                      n_threads=int(c.get("num_host_threads", 4)),
                                      target_velocity=self.env.target_velocity_list or 0.0)
+        elif env_backend is None and c.get("env_backend", "synthetic") == "device":
+            # extension: the device env plane (the same stand-in stepped by a HIP kernel on the
+            # rollout context's stream: no host threads, no copies)
+            from .envs import DeviceVecEnv
+            env_backend = DeviceVecEnv(self.ctx, seed=env_seed, target_velocity=self.env.target_velocity_list or 0.0)
         elif env_backend is None:
             from .envs import SyntheticVecEnv
             env_backend = SyntheticVecEnv(self.n_envs, self.cfg.obs_full_dim, self.device, seed=env_seed)
@@ -502,7 +507,7 @@ class PPOTrainer:
         return ectx
 
     def evaluate(self, num_episodes=100, num_steps=1000, explore=True, tvel=None, n_envs=None,
-                 env_filter="continue", seed=0):
+                 env_filter="continue", seed=0, env_backend="host"):
         """Run the current policies for whole episodes over the host env plane and return the
         reference's tuple (reward_eps, steps_eps, dist_eps, power_total_eps, vel_eps, cot_eps) of
         evaluation/rollout_episodes.py:26-164, one entry per episode.
@@ -520,22 +525,30 @@ class PPOTrainer:
         copy, not updated, "fresh": a new filter, updating (what the reference's separate
         evaluation process gets).  The per-policy filters are applied without updates, as RLlib's
         compute_action does.  The training context, its env backend and the noise generator are
-        not touched: evaluation runs on its own context, env plane and generator (`seed`)."""
-        return self._evaluate(num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed)[0]
+        not touched: evaluation runs on its own context, env plane and generator (`seed`).
 
-    def _evaluate(self, num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed, sens_steps=None):
+        env_backend: "host" (the default) steps the envs on host threads; "device" steps them in
+        a kernel on the evaluation context's stream (ddrl_eval_devenv: no copies, one
+        synchronization per progress poll), and n_envs then defaults to min(num_episodes, 4096)."""
+        return self._evaluate(num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed,
+                              env_backend=env_backend)[0]
+
+    def _evaluate(self, num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed, sens_steps=None,
+                  env_backend="host"):
         """The body of evaluate / evaluate_sensitivity: (six lists, per-policy sensitivity results or
         None).  sens_steps: a function of the evaluation context returning the per-policy steps;
         with it, the C++ loop runs the sensitivity kernel after every action."""
         if env_filter not in ("continue", "frozen", "fresh"):
             raise ValueError(f"env_filter {env_filter!r}: 'continue', 'frozen' or 'fresh'")
+        if env_backend not in ("host", "device"):
+            raise ValueError(f"env_backend {env_backend!r}: 'host' or 'device'")
         if self.cfg.model_kind != N.MODEL_FFN:
             raise N.DdrlError("evaluation: fcnet models only")
         torch, cfg = self.torch, self.cfg
         num_episodes, num_steps = int(num_episodes), int(num_steps)
         if num_episodes < 1 or num_steps < 1:
             raise ValueError("num_episodes and num_steps must be >= 1")
-        n_envs = int(n_envs or min(num_episodes, 128))
+        n_envs = int(n_envs or min(num_episodes, 4096 if env_backend == "device" else 128))
         E = -(-num_episodes // n_envs)
         ectx = self._eval_context(n_envs)
         D = cfg.obs_full_dim
@@ -544,8 +557,12 @@ class PPOTrainer:
         else:
             ectx.filter_set(*self.rctx.filter_get())
         tv = [float(tvel)] if tvel else [float(v) for v in (self.env.target_velocity_list or [0.0])]
-        henv = N.HostEnv(n_envs, D, n_threads=int(self.config.get("num_host_threads", 4)), seed=seed,
-                         target_velocity=tv if len(tv) > 1 else tv[0])
+        if env_backend == "device":
+            henv = N.DevEnv(ectx, seed=seed, target_velocity=tv if len(tv) > 1 else tv[0])
+        else:
+            henv = N.HostEnv(n_envs, D, n_threads=int(self.config.get("num_host_threads", 4)), seed=seed,
+                             target_velocity=tv if len(tv) > 1 else tv[0])
+        run = ectx.eval_devenv if env_backend == "device" else ectx.eval_hostenv
         try:
             henv.set_time_limit(num_steps)
             max_steps = E * num_steps   # every env has had E episodes by then
@@ -557,7 +574,7 @@ class PPOTrainer:
             ectx.eval_begin(E, filter_update=env_filter != "frozen")
             if sens_steps is not None:
                 ectx.eval_sens_begin(sens_steps(ectx))
-            ectx.eval_hostenv(henv, eps, max_steps if explore else 0, max_steps, poll_every=min(25, num_steps))
+            run(henv, eps, max_steps if explore else 0, max_steps, poll_every=min(25, num_steps))
             rows = ectx.eval_results().reshape(-1, 6)
             sens = None
             if sens_steps is not None:
@@ -573,7 +590,7 @@ class PPOTrainer:
         return (reward, [int(s) for s in steps], dist, power, vel, cot), sens
 
     def evaluate_sensitivity(self, num_episodes=10, num_steps=1000, rel_step=0.1, steps=None, tvel=None, n_envs=None,
-                             env_filter="continue", seed=0, explore=True):
+                             env_filter="continue", seed=0, explore=True, env_backend="host"):
         """evaluate() plus the importance matrix of the reference's
         evaluation/rollout_episodes_compute_gradient.py:59-68, :111-122: at every control step every
         input of every policy row is moved by -h_f / +h_f and the difference of the clipped action
@@ -587,7 +604,7 @@ class PPOTrainer:
         (an extension: the reference only runs the filtered centralized policy) h_f = rel_step * 1.0,
         the env-normalized columns having unit scale.  `steps` ({policy_id: [d]} or a per-policy
         list) overrides both.  Every policy of every architecture gets a matrix; constant inputs
-        (the LegID one-hot) are not moved and their rows stay zero."""
+        (the LegID one-hot) are not moved and their rows stay zero.  env_backend as in evaluate()."""
         from .evaluation import default_sens_steps
 
         def sens_steps(ectx):
@@ -607,7 +624,8 @@ class PPOTrainer:
                 out.append(h)
             return out
 
-        return self._evaluate(num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed, sens_steps)
+        return self._evaluate(num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed, sens_steps,
+                              env_backend=env_backend)
 
     def compute_action(self, obs, policy_id=None, explore=None, seed=None, agent_id=None):
         """Trainer.compute_action for one agent observation (the policy's input row, as the env
@@ -651,11 +669,11 @@ class PPOTrainer:
     def stop(self):
         for ectx in self.__dict__.pop("_eval_ctx", {}).values():
             ectx.close()
+        if hasattr(self.backend, "close"):   # first: a device env plane is destroyed before its context
+            self.backend.close()
         if self.rctx is not self.ctx:
             self.rctx.close()
         self.ctx.close()
-        if hasattr(self.backend, "close"):
-            self.backend.close()
 
 
 class _EnvHandle:

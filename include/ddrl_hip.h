@@ -218,6 +218,56 @@ int ddrl_rollout_hostenv(ddrl_ctx* ctx, ddrl_hostenv* env, int groups, const flo
 int ddrl_hostenv_kin(ddrl_hostenv* env, float** kin);
 int ddrl_hostenv_set_time_limit(ddrl_hostenv* env, int steps);
 int ddrl_hostenv_reset_episodes(ddrl_hostenv* env);
+/* The packed fp64 state of every env, DDRL_ENV_STATE_DOUBLES doubles per env, env-major:
+ *   [0..9]   torso {x, y, z, vx, vy, vz, roll, pitch, wroll, wpitch}
+ *   [10..17] joint angles q, [18..25] joint velocities qd, [26..33] last joint forces qfrc
+ *            (joints: FL hip, FL knee, HL hip, HL knee, HR hip, HR knee, FR hip, FR knee)
+ *   [34..37] last contact force per foot, [38] steps of the episode, [39] episode number,
+ *   [40]     target velocity of the episode.
+ * n == n_envs * DDRL_ENV_STATE_DOUBLES.  state_set replaces the state only: the output buffers
+ * (obs, fw, cfrc, kin, done) keep their contents until the next step.  The device env plane
+ * (below) exchanges the same layout, so a running env can be handed from one plane to the other. */
+#define DDRL_ENV_STATE_DOUBLES 41
+int ddrl_hostenv_state_get(ddrl_hostenv* env, double* host, size_t n);
+int ddrl_hostenv_state_set(ddrl_hostenv* env, const double* host, size_t n);
+
+/* Device env plane (devenv.hip): the same stand-in dynamics (one source, csrc/envdyn.h) stepped by a
+ * HIP kernel on the context's stream, four lanes per env (one per leg), the state in device
+ * memory.  Bound to a context: device, stream, n_envs and obs_full_dim (43 or 44) are the
+ * context's.  It emits the host plane's buffers in device memory (ddrl_devenv_buffers):
+ * obs[N][D], fw[N], cfrc[N][14][6], kin[N][9] (written before a done env is reset), done[N].
+ * Every call below is asynchronous on the context's stream unless it says otherwise, and
+ * reports through ddrl_last_error().  Integer arithmetic, the hash, + - * / and the conversions
+ * match the host plane bit for bit (the kernels are built without fp contraction); sin / cos are
+ * the device library's and may differ from the host's in the last places, which reaches the torso
+ * state and the foot forces but not the joints ("Device env plane").
+ *   create: seed and target_velocity as ddrl_hostenv_create; destroy the env before its context
+ *     (an env whose context was destroyed first only accepts destroy);
+ *   reset / reset_episodes / reset_state / set_time_limit / set_target_velocities /
+ *     target_velocities (synchronizes): the host plane's calls of the same names;
+ *   step: actions_dev[N][8] (clipped to [-1, 1]) -> one launch, no synchronization;
+ *   state_get / state_set: the packed layout above; both synchronize. */
+typedef struct ddrl_devenv ddrl_devenv;
+int ddrl_devenv_create(ddrl_ctx* ctx, uint64_t seed, float target_velocity, ddrl_devenv** out);
+int ddrl_devenv_destroy(ddrl_devenv* env);
+int ddrl_devenv_buffers(ddrl_devenv* env, float** obs_dev, float** fw_dev, float** cfrc_dev, float** kin_dev,
+                        uint8_t** done_dev);
+int ddrl_devenv_reset(ddrl_devenv* env);
+int ddrl_devenv_reset_episodes(ddrl_devenv* env);
+int ddrl_devenv_reset_state(ddrl_devenv* env);
+int ddrl_devenv_set_time_limit(ddrl_devenv* env, int steps);
+int ddrl_devenv_set_target_velocities(ddrl_devenv* env, const float* list, int n);
+int ddrl_devenv_target_velocities(ddrl_devenv* env, float* out, int n_envs);
+int ddrl_devenv_step(ddrl_devenv* env, const float* actions_dev);
+int ddrl_devenv_state_get(ddrl_devenv* env, double* host, size_t n);
+int ddrl_devenv_state_set(ddrl_devenv* env, const double* host, size_t n);
+/* A fragment over the device env plane, one in-order chain on the context's stream with no
+ * host wait: if reset, ddrl_devenv_reset and observe(env.obs); then for t in [0, T): act(t) ->
+ * devenv_step -> reward(t, env.fw, env.cfrc, actions, env.done) -> observe(env.obs); then the
+ * bootstrap.  eps_dev[T][N][n_agents][A].  The loop is captured once per (env, eps_dev, env
+ * settings) into a HIP graph and replayed (DDRL_ROLLOUT_GRAPH=0 at context creation issues the
+ * launches directly); any model kind. */
+int ddrl_rollout_devenv(ddrl_ctx* ctx, ddrl_devenv* env, const float* eps_dev, int reset);
 
 /* Evaluation of the context's policies over whole episodes (evaluation/rollout_episodes.py:26-164):
  * N envs x E episodes each instead of the reference's sequential episodes.  fcnet models only.
@@ -260,6 +310,11 @@ int ddrl_eval_end(ddrl_ctx* ctx);
  * steps_run (may be NULL): env steps taken. */
 int ddrl_eval_hostenv(ddrl_ctx* ctx, ddrl_hostenv* env, const float* eps_dev, int eps_steps, int max_steps,
                       int poll_every, int* steps_run);
+/* The same loop over the device env plane, its buffers read in place: reset_episodes, then per
+ * step eval_act -> eval_sens (with the mode on) -> devenv_step -> eval_step.  No copies; the only
+ * synchronization is the progress poll every poll_every steps. */
+int ddrl_eval_devenv(ddrl_ctx* ctx, ddrl_devenv* env, const float* eps_dev, int eps_steps, int max_steps,
+                     int poll_every, int* steps_run);
 /* Input sensitivity ("importance matrix") of the evaluated policies
  * (evaluation/rollout_episodes_compute_gradient.py:59-68, :111-122, :167-168): at every step, every
  * non-constant input feature f of every (env, slot) row is moved by -h_f and +h_f, the 2d perturbed
