@@ -1255,6 +1255,17 @@ static int chk_env(const ddrl_devenv* e) {
 #define CHK_ENV(e) \
   if (chk_env(e)) return -1
 
+// The terrain settings into the kernel arguments.  A captured fragment has them baked into its
+// step nodes, so a change that a terrain launch would see (before or after it) re-keys the graph;
+// flat to flat (new_terrain on flat ground) changes nothing a flat launch reads.
+static void devenv_put_terrain(ddrl_devenv* e, const envdyn::Terrain& t) {
+  DevEnvArgs& a = e->a;
+  const int was_on = a.ter_on;
+  a.ter_lo = t.lo; a.ter_hi = t.hi; a.ter_bump = t.bump_scale; a.ter_inv_bump = t.inv_bump; a.ter_gen = t.generation;
+  a.ter_on = envdyn::terrain_on(t) ? 1 : 0;
+  if (was_on || a.ter_on) ++e->gen;
+}
+
 int ddrl_devenv_create(ddrl_ctx* c, uint64_t seed, float target_velocity, ddrl_devenv** out) {
   CHK_CTX(c);
   if (!out) return fail("ddrl_devenv_create: null output pointer");
@@ -1271,6 +1282,7 @@ int ddrl_devenv_create(ddrl_ctx* c, uint64_t seed, float target_velocity, ddrl_d
   const size_t N = g.n_envs;
   DevEnvArgs& a = e->a;
   a.N = g.n_envs; a.D = g.obs_full_dim; a.time_limit = 1000; a.n_tv = 1; a.seed = seed;
+  devenv_put_terrain(e, envdyn::terrain_flat());
   e->tv_cap = 16;
   e->tv_list.assign(1, (double)target_velocity);
   // the create-time velocity until the first reset draws one, as the host plane
@@ -1363,6 +1375,42 @@ int ddrl_devenv_target_velocities(ddrl_devenv* e, float* out, int n) {
   HIPCHK(hipMemcpyAsync(tv.data(), e->a.st + (size_t)38 * n, (size_t)n * 8, hipMemcpyDeviceToHost, e->ctx->stream));
   HIPCHK(hipStreamSynchronize(e->ctx->stream));
   for (int i = 0; i < n; ++i) out[i] = (float)tv[i];
+  return 0;
+}
+
+int ddrl_devenv_set_terrain(ddrl_devenv* e, double lo, double hi, double bump_scale, uint32_t generation) {
+  CHK_ENV(e);
+  if (!(0.0 <= lo && lo <= hi && hi <= 1.0))
+    return fail("ddrl_devenv_set_terrain: smoothness bounds must satisfy 0 <= lo <= hi <= 1");
+  if (!(bump_scale > 0.0) || !std::isfinite(bump_scale))
+    return fail("ddrl_devenv_set_terrain: bump_scale must be a finite value > 0");
+  // launches already issued hold their own copy of the arguments: no synchronization
+  devenv_put_terrain(e, envdyn::Terrain{lo, hi, bump_scale, 1.0 / bump_scale, generation});
+  return 0;
+}
+
+int ddrl_devenv_terrain(ddrl_devenv* e, double* lo, double* hi, double* bump_scale, uint32_t* generation) {
+  CHK_ENV(e);
+  if (lo) *lo = e->a.ter_lo;
+  if (hi) *hi = e->a.ter_hi;
+  if (bump_scale) *bump_scale = e->a.ter_bump;
+  if (generation) *generation = e->a.ter_gen;
+  return 0;
+}
+
+int ddrl_devenv_new_terrain(ddrl_devenv* e) {
+  CHK_ENV(e);
+  devenv_put_terrain(e, envdyn::Terrain{e->a.ter_lo, e->a.ter_hi, e->a.ter_bump, e->a.ter_inv_bump, e->a.ter_gen + 1u});
+  return 0;
+}
+
+int ddrl_devenv_terrain_height(ddrl_devenv* e, const int32_t* env_index_dev, const double* xy_dev, int n,
+                               double* out_dev) {
+  CHK_ENV(e);
+  if (!env_index_dev || !xy_dev || !out_dev || n < 0)
+    return fail("ddrl_devenv_terrain_height: n >= 0 points (env_index[n], xy[n][2]) and out[n] in device memory");
+  launch_devenv_terrain_height(e->ctx->stream, e->a, env_index_dev, xy_dev, n, out_dev);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 

@@ -41,6 +41,10 @@ __device__ __forceinline__ void store_state(const DevEnvArgs& A, int e, const En
   A.episode[e] = s.episode;
 }
 
+__device__ __forceinline__ Terrain terrain_of(const DevEnvArgs& A) {
+  return Terrain{A.ter_lo, A.ter_hi, A.ter_bump, A.ter_inv_bump, A.ter_gen};
+}
+
 // the value lane k of the quad holds, in every lane of the quad (quad_perm [k, k, k, k])
 template <int K>
 __device__ __forceinline__ double quad_get(double v) { return dpp_mov_d<K * 0x55>(v); }
@@ -54,6 +58,13 @@ __device__ __forceinline__ double quad_get(double v) { return dpp_mov_d<K * 0x55
 // a shorter chain, not throughput: 9.1 us per launch at 128 envs and 10.0 us at 4096, against
 // 20.5 / 21.6 us for one thread per env running envdyn::step_env, bit-equal to this kernel
 // (profiles/devenv/step_ab.json).
+//
+// kTerrain: the instance for uneven ground.  Each leg lane evaluates the height field under its
+// own foot in every substep (envdyn::ground_height: four lattice hashes and the interpolation,
+// integer and fp64 ALU work, no memory traffic) ahead of its contact force; what does not depend
+// on the point (the field's hash key, the env's smoothness) is formed once per step.  The flat
+// instance contains none of it.
+template <bool kTerrain>
 __global__ void __launch_bounds__(256) k_devenv_step(DevEnvArgs A, const float* __restrict__ actions) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   const int e = g >> 2, leg = g & 3;
@@ -71,10 +82,13 @@ __global__ void __launch_bounds__(256) k_devenv_step(DevEnvArgs A, const float* 
   const double a_h = clip_action(actions[(size_t)e * 8 + hip]), a_k = clip_action(actions[(size_t)e * 8 + knee]);
   const double x0 = t.x;
   double force = 0.0, f0 = 0.0, f1 = 0.0, f2 = 0.0, f3 = 0.0;
+  Ground ground{0, 0.0, 0.0};
+  if constexpr (kTerrain) ground = ground_of(terrain_of(A), A.seed, e, episode);
 #pragma unroll 1
   for (int f = 0; f < kFrameSkip; ++f) {
     double push;
-    leg_contact(t.z, t.vz, q_h, q_k, qd_h, force, push);
+    if constexpr (kTerrain) leg_contact_on(ground, leg, t.x, t.y, t.z, t.vz, q_h, q_k, qd_h, force, push);
+    else leg_contact(t.z, t.vz, q_h, q_k, qd_h, force, push);
     f0 = quad_get<0>(force); f1 = quad_get<1>(force); f2 = quad_get<2>(force); f3 = quad_get<3>(force);
     const double p0 = quad_get<0>(push), p1 = quad_get<1>(push), p2 = quad_get<2>(push), p3 = quad_get<3>(push);
     LegSums sums = leg_sums_zero();
@@ -198,10 +212,31 @@ __global__ void __launch_bounds__(64) k_devenv_pack(DevEnvArgs A, double* packed
   }
 }
 
+// the probe of the height field: one thread per point
+__global__ void __launch_bounds__(64) k_devenv_terrain_height(DevEnvArgs A, const int* __restrict__ env_index,
+                                                              const double* __restrict__ xy, int n,
+                                                              double* __restrict__ out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const int e = env_index[i];
+  if (e < 0 || e >= A.N) {   // the indices are in device memory, unseen by the host: NaN, and no read past the arrays
+    out[i] = __builtin_nan("");
+    return;
+  }
+  out[i] = ground_height(ground_of(terrain_of(A), A.seed, e, A.episode[e]), xy[2 * (size_t)i], xy[2 * (size_t)i + 1]);
+}
+
 }  // namespace
 
 void launch_devenv_step(hipStream_t s, const DevEnvArgs& a, const float* actions) {
-  hipLaunchKernelGGL(k_devenv_step, dim3((4 * a.N + 255) / 256), dim3(256), 0, s, a, actions);
+  if (a.ter_on) hipLaunchKernelGGL(k_devenv_step<true>, dim3((4 * a.N + 255) / 256), dim3(256), 0, s, a, actions);
+  else hipLaunchKernelGGL(k_devenv_step<false>, dim3((4 * a.N + 255) / 256), dim3(256), 0, s, a, actions);
+}
+
+void launch_devenv_terrain_height(hipStream_t s, const DevEnvArgs& a, const int* env_index, const double* xy, int n,
+                                  double* out) {
+  if (n < 1) return;
+  hipLaunchKernelGGL(k_devenv_terrain_height, dim3((n + 63) / 64), dim3(64), 0, s, a, env_index, xy, n, out);
 }
 
 void launch_devenv_reset(hipStream_t s, const DevEnvArgs& a, int mode) {

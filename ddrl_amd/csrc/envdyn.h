@@ -60,6 +60,92 @@ ENVDYN_HD double hash_uniform(uint64_t seed, uint64_t env, uint64_t episode, uin
   return (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
 }
 
+// the same hash in two halves, for callers that draw many values under one (seed, env, episode):
+// hash_draw(hash_key(seed, env, episode), k) == hash_uniform(seed, env, episode, k) bit for bit
+ENVDYN_HD uint64_t hash_key(uint64_t seed, uint64_t env, uint64_t episode) {
+  return seed ^ (env * 0x9E3779B97F4A7C15ull) ^ (episode * 0xBF58476D1CE4E5B9ull);
+}
+ENVDYN_HD double hash_draw(uint64_t key, uint64_t k) {
+  uint64_t z = key ^ (k * 0x94D049BB133111EBull);
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+}
+
+// ---- terrain: a procedural height field, a pure function of (seed, env, generation, episode,
+// smoothness bounds, x, y) -- no stored height map (the reference's create_new_hfield,
+// quantruped_v3.py:25-54, draws uniform(smoothness, 1) on a coarse grid, upsamples it, subtracts
+// the minimum and clears a start patch).
+//
+//   settings   lo <= hi in [0, 1] (1: flat), bump_scale (m), generation; inv_bump = 1.0 / bump_scale
+//              is formed once on the host, by the same division on both planes
+//   smoothness of env e in generation g:  s = hi - us * (hi - lo),
+//              us = 0.5 * (hash_uniform(seed ^ kSmoothSalt, e, g, 0) + 1.0)  in [0, 1)
+//   field id   G = (generation << 32) | episode: every episode of an env walks on new ground (the
+//              reference makes a new field before every evaluation episode), and new_terrain
+//              (generation += 1) renews the ground of every env
+//   cell       gx = clamp(x * inv_bump, -kCellMax, kCellMax), fi = floor(gx), tx = gx - fi, likewise y;
+//              lattice value u(i, j) = 0.5 * (hash_uniform(seed ^ kTerrainSalt, e, G,
+//              (uint32(i) << 32) | uint32(j)) + 1.0)  in [0, 1)
+//   weights    wx = tx * tx * (3.0 - 2.0 * tx), wy likewise (smoothstep: the field is continuous
+//              across cell boundaries and so is its gradient)
+//   interp     a0 = u00 + wx * (u10 - u00);  a1 = u01 + wx * (u11 - u01);  U = a0 + wy * (a1 - a0)
+//              (u_ab: the value at cell (i + a, j + b)); U stays in [0, 1] in fp64 as well
+//   ramp       r = max(|x|, |y|); tr = clamp((r - 0.8) * 0.625, 0, 1); ramp = tr * tr * (3.0 - 2.0 * tr):
+//              exactly 0.0 on the start patch r <= 0.8, 1.0 from r = 2.4 on
+//   height     h = ((1.0 - s) * kElevation) * U * ramp  in [0, 1 - s]
+// The reference's lattice value is s + (1 - s) * u and its height (interp - s) * elevation; the
+// common factor (1 - s) is taken out of the interpolation here, which is the same function, makes
+// s = 1 exactly 0.0 and keeps the bounds exact.  Only floor, + - *, comparisons and integer
+// arithmetic: the two planes agree on h bit for bit.
+struct Terrain {
+  double lo, hi, bump_scale, inv_bump;
+  uint32_t generation;
+};
+ENVDYN_HD Terrain terrain_flat() { return Terrain{1.0, 1.0, 2.0, 1.0 / 2.0, 0u}; }
+// flat ground runs the step without any of this (the same expressions as before terrain existed)
+ENVDYN_HD bool terrain_on(const Terrain& t) { return !(t.lo == 1.0 && t.hi == 1.0); }
+
+constexpr uint64_t kTerrainSalt = 0x7E44A1F0C0DE5EEDull, kSmoothSalt = 0x5300074E55D4A3B1ull;
+constexpr double kElevation = 1.0;            // the reference's hfield z size
+constexpr double kPatch = 0.8, kPatchRim = 0.625;   // cleared start patch; 1 / 1.6, the width of its rim (exact)
+constexpr double kCellMax = 1073741824.0;     // 2^30 cells either way: the cell index fits an int32
+
+// the ground of one env for one step: what does not depend on the point
+struct Ground {
+  uint64_t key;      // hash_key of the field
+  double amp;        // (1 - s) * kElevation
+  double inv_bump;
+};
+ENVDYN_HD double terrain_smoothness(const Terrain& t, uint64_t seed, int e) {
+  const double us = 0.5 * (hash_uniform(seed ^ kSmoothSalt, e, t.generation, 0) + 1.0);
+  return t.hi - us * (t.hi - t.lo);
+}
+ENVDYN_HD Ground ground_of(const Terrain& t, uint64_t seed, int e, uint32_t episode) {
+  const uint64_t G = ((uint64_t)t.generation << 32) | (uint64_t)episode;
+  return Ground{hash_key(seed ^ kTerrainSalt, e, G), (1.0 - terrain_smoothness(t, seed, e)) * kElevation, t.inv_bump};
+}
+ENVDYN_HD double smoothstep01(double t) { return t * t * (3.0 - 2.0 * t); }
+ENVDYN_HD double ground_height(const Ground& g, double x, double y) {
+  const double gx = dmax(-kCellMax, dmin(kCellMax, x * g.inv_bump));
+  const double gy = dmax(-kCellMax, dmin(kCellMax, y * g.inv_bump));
+  const double fi = __builtin_floor(gx), fj = __builtin_floor(gy);
+  const double wx = smoothstep01(gx - fi), wy = smoothstep01(gy - fj);
+  const uint32_t i = (uint32_t)(int32_t)fi, j = (uint32_t)(int32_t)fj;
+  const uint64_t i0 = (uint64_t)i << 32, i1 = (uint64_t)(i + 1u) << 32;
+  const uint64_t j0 = j, j1 = j + 1u;
+  const double u00 = 0.5 * (hash_draw(g.key, i0 | j0) + 1.0), u10 = 0.5 * (hash_draw(g.key, i1 | j0) + 1.0);
+  const double u01 = 0.5 * (hash_draw(g.key, i0 | j1) + 1.0), u11 = 0.5 * (hash_draw(g.key, i1 | j1) + 1.0);
+  const double a0 = u00 + wx * (u10 - u00);
+  const double a1 = u01 + wx * (u11 - u01);
+  const double U = a0 + wy * (a1 - a0);
+  const double r = dmax(dabs(x), dabs(y));
+  const double ramp = smoothstep01(dmax(0.0, dmin(1.0, (r - kPatch) * kPatchRim)));
+  return g.amp * U * ramp;
+}
+
 // random.choice(target_velocity_list): every list position equally likely (a repeated value
 // counts once per position); draw index kTvDraw of the episode's counter stream
 ENVDYN_HD double draw_tv(uint64_t seed, int e, uint32_t ep, const double* tv_list, int n_tv) {
@@ -138,6 +224,27 @@ ENVDYN_HD void leg_contact(double z, double vz, double q_hip, double q_knee, dou
   push = force * 0.05 * (-qd_hip) * cos(q_hip);
 }
 
+// leg_contact on uneven ground: the foot's ground height is the field under the foot's world
+// position -- the torso's (x, y), the leg's fixed offset (front / side signs as in accum_leg) and
+// the hip swing's x displacement of the shin -- and the flat expression's fz is lowered by it.
+// The joints do not feel the ground (joint_step reads no force), unhealthy() keeps the absolute
+// height test and the thrust has no slope term, as on flat ground.
+// The leg's offset from the torso's centre: the Ant's foot tips at rest, 0.8 m out in x and in y
+// (hip at 0.2, upper leg to 0.4, lower leg to 0.8).  A fresh episode so starts with the torso on
+// the cleared patch and the feet on its edge: a leg that swings outwards steps onto rising ground.
+constexpr double kFootDX = 0.8, kFootDY = 0.8;
+ENVDYN_HD void leg_contact_on(const Ground& g, int leg, double x, double y, double z, double vz, double q_hip,
+                              double q_knee, double qd_hip, double& force, double& push) {
+  const double ck = cos(q_knee), sh = sin(q_hip), ch = cos(q_hip);
+  const double side = (leg == 0 || leg == 1) ? 1.0 : -1.0;
+  const double front = (leg == 0 || leg == 3) ? 1.0 : -1.0;
+  const double h = ground_height(g, x + front * kFootDX + kShin * ck * sh, y + side * kFootDY);
+  const double fz = z - kShin * ck * ch + kHipOff * dabs(sh) - h;
+  force = 0.0;
+  if (fz < 0.0) force = dmax(0.0, -kGround * fz - kGroundDamp * vz);
+  push = force * 0.05 * (-qd_hip) * ch;
+}
+
 // the four per-leg terms summed over the legs in the order 0, 1, 2, 3 from 0.0
 struct LegSums {
   double thrust, lift, troll, tpitch;
@@ -208,8 +315,11 @@ ENVDYN_HD bool unhealthy(double z) { return !(z > 0.1 && z < 1.5) || !__builtin_
 
 // One env step for one thread: the actions a8[8] into the state and the env's outputs
 // (obs [D], fw, cfrc [14][6], kin [9] = {dx, qd[0..7]} before a done env is reset, done).
+// terrain: null on flat ground (the flat leg_contact), else the settings of an uneven field.
 ENVDYN_HD void step_env(EnvState& s, const float* a8, float* obs, float* fw, float* cf, float* kn, uint8_t* done,
-                        int D, int time_limit, uint64_t seed, int e, const double* tv_list, int n_tv) {
+                        int D, int time_limit, uint64_t seed, int e, const double* tv_list, int n_tv,
+                        const Terrain* terrain = nullptr) {
+  const Ground g = terrain ? ground_of(*terrain, seed, e, s.episode) : Ground{0, 0.0, 0.0};
   double a[8];
   for (int j = 0; j < 8; ++j) a[j] = clip_action(a8[j]);
   const double x0 = s.x;
@@ -219,7 +329,8 @@ ENVDYN_HD void step_env(EnvState& s, const float* a8, float* obs, float* fw, flo
     for (int leg = 0; leg < 4; ++leg) {
       const int hip = 2 * leg, knee = hip + 1;
       double force, push;
-      leg_contact(t.z, t.vz, s.q[hip], s.q[knee], s.qd[hip], force, push);
+      if (terrain) leg_contact_on(g, leg, t.x, t.y, t.z, t.vz, s.q[hip], s.q[knee], s.qd[hip], force, push);
+      else leg_contact(t.z, t.vz, s.q[hip], s.q[knee], s.qd[hip], force, push);
       s.foot[leg] = force;
       accum_leg(sums, leg, force, push);
     }

@@ -95,7 +95,8 @@ void ddrl_hostenv::write_obs(int e, const double* ctrl) { envdyn::write_obs(st[e
 
 void ddrl_hostenv::step_env(int e, const float* a8) {
   envdyn::step_env(st[e], a8, obs + (size_t)e * D, fw + e, cfrc + (size_t)e * 14 * 6, kin + (size_t)e * 9, done + e, D,
-                   time_limit, seed, e, tv_list.data(), (int)tv_list.size());
+                   time_limit, seed, e, tv_list.data(), (int)tv_list.size(),
+                   envdyn::terrain_on(terrain) ? &terrain : nullptr);
 }
 
 void ddrl_hostenv::state_get(double* out) const {
@@ -263,6 +264,65 @@ extern "C" int ddrl_hostenv_reset_state(ddrl_hostenv* h) {
     return -1;
   }
   h->reset_state();
+  return 0;
+}
+
+extern "C" int ddrl_hostenv_set_terrain(ddrl_hostenv* h, double lo, double hi, double bump_scale, uint32_t generation) {
+  if (!h) {
+    g_henv_err = "null host env";
+    return -1;
+  }
+  if (!(0.0 <= lo && lo <= hi && hi <= 1.0)) {
+    g_henv_err = "ddrl_hostenv_set_terrain: smoothness bounds must satisfy 0 <= lo <= hi <= 1";
+    return -1;
+  }
+  if (!(bump_scale > 0.0) || !std::isfinite(bump_scale)) {
+    g_henv_err = "ddrl_hostenv_set_terrain: bump_scale must be a finite value > 0";
+    return -1;
+  }
+  h->terrain = envdyn::Terrain{lo, hi, bump_scale, 1.0 / bump_scale, generation};
+  return 0;
+}
+
+extern "C" int ddrl_hostenv_terrain(ddrl_hostenv* h, double* lo, double* hi, double* bump_scale, uint32_t* generation) {
+  if (!h) {
+    g_henv_err = "null host env";
+    return -1;
+  }
+  if (lo) *lo = h->terrain.lo;
+  if (hi) *hi = h->terrain.hi;
+  if (bump_scale) *bump_scale = h->terrain.bump_scale;
+  if (generation) *generation = h->terrain.generation;
+  return 0;
+}
+
+extern "C" int ddrl_hostenv_new_terrain(ddrl_hostenv* h) {
+  if (!h) {
+    g_henv_err = "null host env";
+    return -1;
+  }
+  ++h->terrain.generation;
+  return 0;
+}
+
+extern "C" int ddrl_hostenv_terrain_height(ddrl_hostenv* h, const int32_t* env_index, const double* xy, int n,
+                                           double* out) {
+  if (!h || !env_index || !xy || !out || n < 0) {
+    g_henv_err = "ddrl_hostenv_terrain_height: a host env, n >= 0 points (env_index[n], xy[n][2]) and out[n]";
+    return -1;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (env_index[i] < 0 || env_index[i] >= h->N) {
+      g_henv_err = "ddrl_hostenv_terrain_height: env index out of range";
+      return -1;
+    }
+  }
+  h->pool->parallel_for(n, [&](int p0, int p1) {
+    for (int i = p0; i < p1; ++i) {
+      const int e = env_index[i];
+      out[i] = envdyn::ground_height(envdyn::ground_of(h->terrain, h->seed, e, h->st[e].episode), xy[2 * i], xy[2 * i + 1]);
+    }
+  });
   return 0;
 }
 

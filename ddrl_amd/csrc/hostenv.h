@@ -16,6 +16,13 @@
 // env is reset at once (its next observation is the reset one), as RLlib's sampler does.
 // Every env is a pure function of (seed, env index, its own actions): results do not depend on
 // the thread count or on how the envs are grouped.
+//
+// Uneven ground (the reference's hf_smoothness / create_new_hfield) is a procedural height field,
+// envdyn.h's "terrain": each foot's contact height is lowered by the field under that foot, so
+// feet on differing ground give uneven lift and roll / pitch torque, and the contact forces reach
+// cfrc and the rewards.  What it is not: the joints do not feel the ground, unhealthy(z) keeps the
+// absolute torso height test (as the reference's env does), and the thrust has no slope term.
+// With the settings at their defaults (lo = hi = 1) the step runs the flat expressions unchanged.
 #pragma once
 #include <condition_variable>
 #include <cstdint>
@@ -66,6 +73,9 @@ struct ddrl_hostenv {
   // before a done env is reset (evaluation's distance and power need the episode's last step)
   float* kin = nullptr;
   int time_limit = 1000;   // gym TimeLimit of the registered envs (simulation_envs/__init__.py:27-32)
+  // the ground (envdyn.h, "terrain"): flat until set_terrain says otherwise; new_terrain is the
+  // reference's create_new_random_hfield (generation += 1)
+  envdyn::Terrain terrain = envdyn::terrain_flat();
   bool pinned = false;
   hostenv::Pool* pool = nullptr;
 

@@ -206,9 +206,19 @@ struct DevEnvArgs {
   const double* tv_list;     // [n_tv]
   float *obs, *fw, *cfrc, *kin;   // [N][D], [N], [N][14][6], [N][9]
   uint8_t* done;             // [N]
+  // the ground (envdyn::Terrain): smoothness bounds, bump spacing and its inverse, generation;
+  // ter_on: not flat (lo == hi == 1 is flat), which selects the terrain instance of the step kernel
+  double ter_lo, ter_hi, ter_bump, ter_inv_bump;
+  unsigned ter_gen;
+  int ter_on;
 };
 enum { DEVENV_RESET_ALL = 0, DEVENV_RESET_EPISODES = 1, DEVENV_RESET_STATE = 2 };
-void launch_devenv_step(hipStream_t s, const DevEnvArgs& a, const float* actions);   // four lanes per env
+// four lanes per env; the flat instance, or with a.ter_on the instance that evaluates the height
+// field under every foot
+void launch_devenv_step(hipStream_t s, const DevEnvArgs& a, const float* actions);
+// out[n] = the ground height of env env_index[i] (its current episode's field) at (xy[2i], xy[2i+1])
+void launch_devenv_terrain_height(hipStream_t s, const DevEnvArgs& a, const int* env_index, const double* xy, int n,
+                                  double* out);
 void launch_devenv_reset(hipStream_t s, const DevEnvArgs& a, int mode);
 // packed[N][41] (DDRL_ENV_STATE_DOUBLES) <- state, or state <- packed when unpack
 void launch_devenv_pack(hipStream_t s, const DevEnvArgs& a, double* packed, int unpack);

@@ -3,8 +3,12 @@ evaluation/evaluate_trained_policies_pd.py:84-127): run a restored trainer for w
 report, per episode, reward, duration, distance, power, velocity and cost of transport.
 
 The episodes run on the device path (PPOTrainer.evaluate: ddrl_eval_hostenv over the host env
-plane), n_envs envs side by side with a quota of episodes each, not one after another.  The
-stand-in env has no terrain: `hf_smoothness` is carried into the rows as a label only.
+plane, or ddrl_eval_devenv over the device env plane), n_envs envs side by side with a quota of
+episodes each, not one after another.  `hf_smoothness` is the smoothness of the ground the
+evaluation env plane is created with (the stand-in's procedural height field, csrc/envdyn.h): 1.0
+is flat, and every episode of every env runs on ground of its own, as the reference regenerates
+the field before every episode (evaluation/rollout_episodes.py:79).  The `evaluated_on` column of
+evaluate_checkpoints' rows is the smoothness the episodes really ran on.
 """
 from __future__ import annotations
 
@@ -18,19 +22,20 @@ COLUMNS = ["approach", "seed", "trained_on", "evaluated_on", "simulation_run", "
 
 
 def rollout_episodes(env, agent, num_episodes=1, num_steps=1000, render=False, explore_during_rollout=None,
-                     tvel=None, **evaluate_args):
+                     tvel=None, hf_smoothness=None, **evaluate_args):
     """rollout_episodes(env, agent, ...) of the reference: `agent` is a ddrl_amd PPOTrainer; `env` is
     accepted for the signature (the trainer evaluates on its own env plane; tvel sets the
     one-entry target-velocity list as the reference does on `env`, :38-39).  Returns
     (reward_eps, steps_eps, dist_eps, power_total_eps, vel_eps, cot_eps).
     explore_during_rollout None samples, as the reference's compute_action call without `explore`
     does (:103-107); False takes the action mean.  evaluate_args go to PPOTrainer.evaluate
-    (n_envs, env_filter, seed)."""
+    (n_envs, env_filter, seed, env_backend).  hf_smoothness: the ground's smoothness; None takes
+    the trainer's env_config value (1.0 unless set)."""
     if render:
         raise NotImplementedError("rendering is out of scope: the host env plane has no viewer")
     explore = True if explore_during_rollout is None else bool(explore_during_rollout)
     return agent.evaluate(num_episodes=num_episodes, num_steps=num_steps, explore=explore, tvel=tvel,
-                          **evaluate_args)
+                          hf_smoothness=hf_smoothness, **evaluate_args)
 
 
 def default_sens_steps(n, S, rel_step=0.1, M=None):
@@ -72,21 +77,22 @@ def evaluate_checkpoints(config, checkpoint_paths, approach, hf_smoothness=1.0, 
                          seeds=None, trained_on="flat", n_envs=None, device=0, **evaluate_args):
     """evaluate_trained_policies_pd.py:84-127 for one approach: per checkpoint, build a trainer
     from `config`, restore the RLlib checkpoint, roll out num_episodes episodes and return one
-    row (a dict with the reference's DataFrame columns, COLUMNS) per episode."""
+    row (a dict with the reference's DataFrame columns, COLUMNS) per episode.  The episodes run
+    on ground of smoothness hf_smoothness (the reference passes it as the env's hf_smoothness,
+    :100-103); `evaluated_on` carries it."""
     from .trainer import PPOTrainer
     rows = []
     for k, path in enumerate(checkpoint_paths):
-        cfg = {**config, "env_config": {**config.get("env_config", {}), "hf_smoothness": hf_smoothness}}
-        agent = PPOTrainer(cfg, n_envs=8, device=device)   # the training shard is not used: a small one
+        agent = PPOTrainer(config, n_envs=8, device=device)   # the training shard is not used: a small one
         try:
             agent.restore_rllib(path)
             res = rollout_episodes(None, agent, num_episodes=num_episodes, num_steps=num_steps, n_envs=n_envs,
-                                   **evaluate_args)
+                                   hf_smoothness=hf_smoothness, **evaluate_args)
         finally:
             agent.stop()
         seed = seeds[k] if seeds is not None else k
         for it in range(len(res[0])):
-            rows.append({"approach": approach, "seed": seed, "trained_on": trained_on, "evaluated_on": hf_smoothness,
+            rows.append({"approach": approach, "seed": seed, "trained_on": trained_on, "evaluated_on": float(hf_smoothness),
                          "simulation_run": it, "reward": res[0][it], "duration": res[1][it], "distance": res[2][it],
                          "power": res[3][it], "velocity": res[4][it], "CoT": res[5][it]})
     return rows

@@ -21,6 +21,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import native as N
+from .envs import curriculum_bounds, curriculum_of
 from .simulation_envs import get_env_class
 
 
@@ -37,6 +38,9 @@ class HostMultiAgentEnv:
         # every env draws random.choice(target_velocity_list) on each reset
         # (quantruped_adaptor_multi_environment.py:47-50, :214-216), in the env plane
         self.env = N.HostEnv(self.n, self.D, n_threads, seed, [float(v) for v in tv] if tv else 0.0)
+        # the ground: env_config's hf_smoothness (adaptor :34-44), and the curriculum of :66-75
+        self.env.set_terrain(float(self.spec.hf_smoothness))
+        self.curriculum = curriculum_of(self.spec.config)
         self.clip = filter_clip
         # env-side MeanStdFilter singleton: RunningStat (n, M, S), fp64
         self.rs_n, self.rs_M, self.rs_S = 0, np.zeros(self.D), np.zeros(self.D)
@@ -126,11 +130,29 @@ class HostMultiAgentEnv:
     def update_environment_after_epoch(self, timesteps_total):
         """The curriculum hook RLlib calls on every env after each training iteration
         (on_train_result, train_experiment_1_architecture_on_flat.py:171-178; adaptor :97-122):
-        the spec's update_after_epoch, then env.reset() of every env (state and TimeLimit count
-        restart, target velocity kept, the observation of that reset discarded).  The terrain
-        regeneration (create_new_random_hfield) is MuJoCo-side and out of scope."""
+        the spec's update_after_epoch; with curriculum_learning the smoothness interval of adaptor
+        :104-120 (ddrl_amd.envs.curriculum_bounds), from which every env draws its smoothness; new
+        ground (create_new_random_hfield); then env.reset() of every env (state and TimeLimit count
+        restart, target velocity kept, the observation of that reset discarded)."""
         self.spec.update_after_epoch(timesteps_total)
+        if self.curriculum is not None:
+            lo, hi = curriculum_bounds(*self.curriculum, timesteps_total)
+            self.env.set_terrain(lo, hi, self.env.terrain["bump_scale"])
+        self.create_new_random_hfield()
         self.env.reset_state()
+
+    def create_new_random_hfield(self):
+        """quantruped_v3.py:152-154: new ground for every env (the next terrain generation)."""
+        self.env.new_terrain()
+
+    def set_hf_parameter(self, smoothness, bump_scale=None):
+        """quantruped_v3.py:156-161: the smoothness (and bump spacing) of the ground made from now
+        on; the ground itself changes with it at once, the field being a function of its settings."""
+        self.env.set_terrain(smoothness, None, self.env.terrain["bump_scale"] if bump_scale is None else bump_scale)
+
+    @property
+    def terrain(self):
+        return self.env.terrain
 
     @property
     def target_velocities(self):

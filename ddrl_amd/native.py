@@ -131,6 +131,16 @@ _SIGS = {
     "ddrl_hostenv_reset_episodes": ([VP], C.c_int),
     "ddrl_hostenv_state_get": ([VP, VP, C.c_size_t], C.c_int),
     "ddrl_hostenv_state_set": ([VP, VP, C.c_size_t], C.c_int),
+    "ddrl_hostenv_set_terrain": ([VP, C.c_double, C.c_double, C.c_double, C.c_uint32], C.c_int),
+    "ddrl_hostenv_terrain": ([VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.POINTER(C.c_uint32)], C.c_int),
+    "ddrl_hostenv_new_terrain": ([VP], C.c_int),
+    "ddrl_hostenv_terrain_height": ([VP, VP, VP, C.c_int, VP], C.c_int),
+    "ddrl_devenv_set_terrain": ([VP, C.c_double, C.c_double, C.c_double, C.c_uint32], C.c_int),
+    "ddrl_devenv_terrain": ([VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                             C.POINTER(C.c_uint32)], C.c_int),
+    "ddrl_devenv_new_terrain": ([VP], C.c_int),
+    "ddrl_devenv_terrain_height": ([VP, VP, VP, C.c_int, VP], C.c_int),
     "ddrl_devenv_create": ([VP, C.c_uint64, f32, C.POINTER(VP)], C.c_int),
     "ddrl_devenv_destroy": ([VP], C.c_int),
     "ddrl_devenv_buffers": ([VP, C.POINTER(VP), C.POINTER(VP), C.POINTER(VP), C.POINTER(VP), C.POINTER(VP)],
@@ -616,6 +626,25 @@ class Context:
                                          _ptr(logits_dev), _ptr(values_dev)))
 
 
+def _terrain_args(lo, hi, generation, current_generation):
+    """(lo, hi, generation) of a set_terrain call: hi None is lo, generation None the current one."""
+    lo = float(lo)
+    hi = lo if hi is None else float(hi)
+    gen = int(current_generation() if generation is None else generation)
+    if not 0 <= gen <= 0xFFFFFFFF:
+        raise DdrlError("set_terrain: generation must fit an unsigned 32-bit integer")
+    return lo, hi, gen
+
+
+def _terrain_points(env_index, xy, n_envs):
+    """(int32 [n], float64 [n][2]) of a terrain_height call, the env indices checked."""
+    pts = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    idx = np.array(np.broadcast_to(np.asarray(env_index, np.int32), (pts.shape[0],)))   # a writable copy
+    if idx.size and (idx.min() < 0 or idx.max() >= n_envs):
+        raise DdrlError(f"terrain_height: env index out of range [0, {n_envs})")
+    return idx, pts
+
+
 class HostEnv:
     """The host env plane (hostenv.cpp): N QuAntruped stand-in envs stepped by a pool of host
     threads into pinned buffers, exposed here as numpy views (obs [N][D], act [N][8], fw [N],
@@ -699,6 +728,37 @@ class HostEnv:
         self._live()
         a = np.ascontiguousarray(state, np.float64)
         self._ck(self.lib.ddrl_hostenv_state_set(self.h, a.ctypes.data, a.size))
+
+    def set_terrain(self, lo, hi=None, bump_scale=2.0, generation=None):
+        """Uneven ground (the reference's hf_smoothness): every env draws its smoothness from
+        [lo, hi] per terrain generation; hi None is the fixed smoothness lo.  1 is flat (the
+        default), 0 the roughest.  bump_scale: metres between bumps (hf_bump_scale).  generation
+        None keeps the current one."""
+        self._live()
+        lo, hi, gen = _terrain_args(lo, hi, generation, lambda: self.terrain["generation"])
+        self._ck(self.lib.ddrl_hostenv_set_terrain(self.h, lo, hi, float(bump_scale), gen))
+
+    @property
+    def terrain(self):
+        """{"lo", "hi", "bump_scale", "generation"} as set_terrain / new_terrain left them."""
+        self._live()
+        lo, hi, bs, gen = C.c_double(), C.c_double(), C.c_double(), C.c_uint32()
+        self._ck(self.lib.ddrl_hostenv_terrain(self.h, C.byref(lo), C.byref(hi), C.byref(bs), C.byref(gen)))
+        return {"lo": lo.value, "hi": hi.value, "bump_scale": bs.value, "generation": gen.value}
+
+    def new_terrain(self):
+        """create_new_random_hfield: the next terrain generation, new ground for every env."""
+        self._live()
+        self._ck(self.lib.ddrl_hostenv_new_terrain(self.h))
+
+    def terrain_height(self, env_index, xy):
+        """The ground height of env env_index[i]'s current field at xy[i] = (x, y); [n] float64."""
+        self._live()
+        idx, pts = _terrain_points(env_index, xy, self.n)
+        out = np.empty(idx.size, np.float64)
+        self._ck(self.lib.ddrl_hostenv_terrain_height(self.h, idx.ctypes.data, pts.ctypes.data, idx.size,
+                                                      out.ctypes.data))
+        return out
 
     @property
     def target_velocities(self):
@@ -791,6 +851,38 @@ class DevEnv:
         self._live()
         tvs = [float(v) for v in tvs]
         _ck(self.lib.ddrl_devenv_set_target_velocities(self.h, (C.c_float * len(tvs))(*tvs), len(tvs)))
+
+    def set_terrain(self, lo, hi=None, bump_scale=2.0, generation=None):
+        """HostEnv.set_terrain for the device plane: holds for the launches issued after it."""
+        self._live()
+        lo, hi, gen = _terrain_args(lo, hi, generation, lambda: self.terrain["generation"])
+        _ck(self.lib.ddrl_devenv_set_terrain(self.h, lo, hi, float(bump_scale), gen))
+
+    @property
+    def terrain(self):
+        """{"lo", "hi", "bump_scale", "generation"} as set_terrain / new_terrain left them."""
+        self._live()
+        lo, hi, bs, gen = C.c_double(), C.c_double(), C.c_double(), C.c_uint32()
+        _ck(self.lib.ddrl_devenv_terrain(self.h, C.byref(lo), C.byref(hi), C.byref(bs), C.byref(gen)))
+        return {"lo": lo.value, "hi": hi.value, "bump_scale": bs.value, "generation": gen.value}
+
+    def new_terrain(self):
+        """create_new_random_hfield: the next terrain generation, new ground for every env."""
+        self._live()
+        _ck(self.lib.ddrl_devenv_new_terrain(self.h))
+
+    def terrain_height(self, env_index, xy):
+        """The ground height of env env_index[i]'s current field at xy[i], computed by a kernel
+        on the context's stream; [n] float64 on the host.  Synchronizes."""
+        import torch
+        self._live()
+        idx, pts = _terrain_points(env_index, xy, self.n)
+        dev = torch.device("cuda", self.ctx.device)
+        idx_d, pts_d = torch.from_numpy(idx).to(dev), torch.from_numpy(pts).to(dev)
+        out = torch.empty(idx.size, dtype=torch.float64, device=dev)
+        _ck(self.lib.ddrl_devenv_terrain_height(self.h, _ptr(idx_d), _ptr(pts_d), idx.size, _ptr(out)))
+        self.ctx.synchronize()
+        return out.cpu().numpy()
 
     @property
     def target_velocities(self):

@@ -74,9 +74,9 @@ class QuantrupedMultiPoliciesEnv:
 
     def update_environment_after_epoch(self, timesteps_total):
         """Curriculum hook (adaptor :97-122), the spec's part: update_after_epoch.  The env
-        reset that follows it in the reference is the backend's (HostMultiAgentEnv /
-        ddrl_amd.envs backends: every env's state and TimeLimit count restart); terrain
-        regeneration is MuJoCo-side and out of scope."""
+        smoothness curriculum, the new ground (create_new_random_hfield) and the env reset that
+        follow it in the reference are the backend's (HostMultiAgentEnv / ddrl_amd.envs backends:
+        set_terrain, new_terrain, then every env's state and TimeLimit count restart)."""
         self.update_after_epoch(timesteps_total)
 
     def update_after_epoch(self, timesteps_total):

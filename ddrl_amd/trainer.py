@@ -50,6 +50,19 @@ def rank_seeds(seed, rank):
     return seed + 1_000_003 * rank, seed + 1 + 1_000_003 * rank
 
 
+_warned_synthetic_terrain = False
+
+
+def _warn_synthetic_terrain():
+    """Once per process: the synthetic backend draws its observations and has no ground."""
+    global _warned_synthetic_terrain
+    if not _warned_synthetic_terrain:
+        import warnings
+        _warned_synthetic_terrain = True
+        warnings.warn("env_config hf_smoothness < 1 has no effect on the synthetic env backend (it has no "
+                      "terrain): use env_backend 'host' or 'device' to train on uneven ground", stacklevel=3)
+
+
 class PPOTrainer:
     """Multi-agent PPO on one device (one env shard).
 
@@ -98,20 +111,27 @@ class PPOTrainer:
                 layer = {v: k for k, v in N.GNN_LAYERS.items()}[self.cfg.gnn_layer]
                 self.ctx.params_set(p, glorot_gnn_flat(self.rng, self.cfg.act_dim, layer=layer))
         self.kl_coeff = [float(c["kl_coeff"])] * P
+        # the ground of the env planes: env_config["hf_smoothness"] (1.0: flat) and the curriculum
+        # keys of the adaptor (curriculum_learning, range_smoothness, range_last_timestep)
+        self.hf_smoothness = float(getattr(self.env, "hf_smoothness", 1.0))
         if env_backend is None and c.get("env_backend", "synthetic") == "host":
             # extension: the host env plane (the QuAntruped stand-in on host threads; TVel
             # target velocities drawn per env from env_config["target_velocity"] on every reset)
-            from .envs import HostVecEnv
+            from .envs import HostVecEnv, curriculum_of
             env_backend = HostVecEnv(self.n_envs, self.cfg.obs_full_dim, self.device, seed=env_seed,
                                      n_threads=int(c.get("num_host_threads", 4)),
-                                     target_velocity=self.env.target_velocity_list or 0.0)
+                                     target_velocity=self.env.target_velocity_list or 0.0,
+                                     hf_smoothness=self.hf_smoothness, curriculum=curriculum_of(getattr(self.env, "config", {})))
         elif env_backend is None and c.get("env_backend", "synthetic") == "device":
             # extension: the device env plane (the same stand-in stepped by a HIP kernel on the
             # rollout context's stream: no host threads, no copies)
-            from .envs import DeviceVecEnv
-            env_backend = DeviceVecEnv(self.ctx, seed=env_seed, target_velocity=self.env.target_velocity_list or 0.0)
+            from .envs import DeviceVecEnv, curriculum_of
+            env_backend = DeviceVecEnv(self.ctx, seed=env_seed, target_velocity=self.env.target_velocity_list or 0.0,
+                                       hf_smoothness=self.hf_smoothness, curriculum=curriculum_of(getattr(self.env, "config", {})))
         elif env_backend is None:
             from .envs import SyntheticVecEnv
+            if self.hf_smoothness < 1.0:
+                _warn_synthetic_terrain()
             env_backend = SyntheticVecEnv(self.n_envs, self.cfg.obs_full_dim, self.device, seed=env_seed)
         self.backend = env_backend
         self.actions = torch.zeros((self.n_envs, 8), dtype=torch.float32, device=self.device)
@@ -507,7 +527,7 @@ class PPOTrainer:
         return ectx
 
     def evaluate(self, num_episodes=100, num_steps=1000, explore=True, tvel=None, n_envs=None,
-                 env_filter="continue", seed=0, env_backend="host"):
+                 env_filter="continue", seed=0, env_backend="host", hf_smoothness=None):
         """Run the current policies for whole episodes over the host env plane and return the
         reference's tuple (reward_eps, steps_eps, dist_eps, power_total_eps, vel_eps, cot_eps) of
         evaluation/rollout_episodes.py:26-164, one entry per episode.
@@ -529,12 +549,17 @@ class PPOTrainer:
 
         env_backend: "host" (the default) steps the envs on host threads; "device" steps them in
         a kernel on the evaluation context's stream (ddrl_eval_devenv: no copies, one
-        synchronization per progress poll), and n_envs then defaults to min(num_episodes, 4096)."""
+        synchronization per progress poll), and n_envs then defaults to min(num_episodes, 4096).
+
+        hf_smoothness: the smoothness of the ground the evaluation env plane is created with (1.0:
+        flat); None takes the trainer's env_config["hf_smoothness"].  Every episode of every env
+        runs on ground of its own (the field is keyed by the env's episode number), as the reference
+        makes a new field before every episode (evaluation/rollout_episodes.py:79)."""
         return self._evaluate(num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed,
-                              env_backend=env_backend)[0]
+                              env_backend=env_backend, hf_smoothness=hf_smoothness)[0]
 
     def _evaluate(self, num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed, sens_steps=None,
-                  env_backend="host"):
+                  env_backend="host", hf_smoothness=None):
         """The body of evaluate / evaluate_sensitivity: (six lists, per-policy sensitivity results or
         None).  sens_steps: a function of the evaluation context returning the per-policy steps;
         with it, the C++ loop runs the sensitivity kernel after every action."""
@@ -565,6 +590,7 @@ class PPOTrainer:
         run = ectx.eval_devenv if env_backend == "device" else ectx.eval_hostenv
         try:
             henv.set_time_limit(num_steps)
+            henv.set_terrain(self.hf_smoothness if hf_smoothness is None else float(hf_smoothness))
             max_steps = E * num_steps   # every env has had E episodes by then
             eps = None
             if explore:
@@ -590,7 +616,7 @@ class PPOTrainer:
         return (reward, [int(s) for s in steps], dist, power, vel, cot), sens
 
     def evaluate_sensitivity(self, num_episodes=10, num_steps=1000, rel_step=0.1, steps=None, tvel=None, n_envs=None,
-                             env_filter="continue", seed=0, explore=True, env_backend="host"):
+                             env_filter="continue", seed=0, explore=True, env_backend="host", hf_smoothness=None):
         """evaluate() plus the importance matrix of the reference's
         evaluation/rollout_episodes_compute_gradient.py:59-68, :111-122: at every control step every
         input of every policy row is moved by -h_f / +h_f and the difference of the clipped action
@@ -604,7 +630,7 @@ class PPOTrainer:
         (an extension: the reference only runs the filtered centralized policy) h_f = rel_step * 1.0,
         the env-normalized columns having unit scale.  `steps` ({policy_id: [d]} or a per-policy
         list) overrides both.  Every policy of every architecture gets a matrix; constant inputs
-        (the LegID one-hot) are not moved and their rows stay zero.  env_backend as in evaluate()."""
+        (the LegID one-hot) are not moved and their rows stay zero.  env_backend and hf_smoothness as in evaluate()."""
         from .evaluation import default_sens_steps
 
         def sens_steps(ectx):
@@ -625,7 +651,7 @@ class PPOTrainer:
             return out
 
         return self._evaluate(num_episodes, num_steps, explore, tvel, n_envs, env_filter, seed, sens_steps,
-                              env_backend=env_backend)
+                              env_backend=env_backend, hf_smoothness=hf_smoothness)
 
     def compute_action(self, obs, policy_id=None, explore=None, seed=None, agent_id=None):
         """Trainer.compute_action for one agent observation (the policy's input row, as the env

@@ -205,8 +205,27 @@ int ddrl_hostenv_target_velocities(ddrl_hostenv* env, float* out, int n_envs);
  * training iteration through on_train_result, train_experiment_1_architecture_on_flat.py:171-178):
  * every env's state and TimeLimit count restart (gym env.reset()), the target velocity is kept,
  * no done flag is raised and obs is not rewritten (the adaptor discards that observation).
- * The terrain regeneration of the same hook is MuJoCo-side (out of scope). */
+ * The terrain regeneration of the same hook is ddrl_hostenv_new_terrain (below). */
 int ddrl_hostenv_reset_state(ddrl_hostenv* env);
+/* Uneven ground (the reference's hf_smoothness and create_new_hfield, quantruped_v3.py:25-54): a
+ * procedural height field, a pure function of (seed, env index, generation, the env's episode
+ * number, smoothness, x, y) with no stored map -- a lattice of uniform values every bump_scale
+ * metres, smoothstep-interpolated, cleared to exactly 0.0 on the start patch max(|x|, |y|) <= 0.8
+ * and rising to full height at 2.4 (csrc/envdyn.h states the operation order; both planes compute
+ * it bit for bit alike).  Each foot's contact height is lowered by the field under that foot.
+ *   set_terrain: every env draws its smoothness from [lo, hi] per generation (lo == hi: fixed);
+ *     1 is flat, 0 the roughest (heights in [0, 1 - smoothness]).  Refuses anything outside
+ *     0 <= lo <= hi <= 1 and bump_scale > 0.  Defaults: 1, 1, 2.0 (the reference's hf_bump_scale),
+ *     generation 0.  With lo == hi == 1 the step is the flat one, unchanged.
+ *   new_terrain: create_new_random_hfield -- generation += 1, new ground for every env.  Within a
+ *     generation every episode of an env has its own ground as well (the field is keyed by the
+ *     episode number; the reference makes a new field before every evaluation episode).
+ *   terrain_height: the probe -- out[i] = the height of env env_index[i]'s current ground at
+ *     (xy[2i], xy[2i + 1]). */
+int ddrl_hostenv_set_terrain(ddrl_hostenv* env, double lo, double hi, double bump_scale, uint32_t generation);
+int ddrl_hostenv_terrain(ddrl_hostenv* env, double* lo, double* hi, double* bump_scale, uint32_t* generation);
+int ddrl_hostenv_new_terrain(ddrl_hostenv* env);
+int ddrl_hostenv_terrain_height(ddrl_hostenv* env, const int32_t* env_index, const double* xy, int n, double* out);
 int ddrl_rollout_hostenv(ddrl_ctx* ctx, ddrl_hostenv* env, int groups, const float* eps_dev, int reset);
 /* What evaluation needs of the env plane.
  *   kin: the pinned buffer kin[N][9] = {torso dx of the step, joint velocities qd[0..7]}, written
@@ -261,11 +280,22 @@ int ddrl_devenv_target_velocities(ddrl_devenv* env, float* out, int n_envs);
 int ddrl_devenv_step(ddrl_devenv* env, const float* actions_dev);
 int ddrl_devenv_state_get(ddrl_devenv* env, double* host, size_t n);
 int ddrl_devenv_state_set(ddrl_devenv* env, const double* host, size_t n);
+/* Uneven ground: the host plane's calls of the same names.  The settings are kernel arguments:
+ * they hold for the launches issued after the call (no synchronization), and with terrain on the
+ * step runs a second instance of the kernel that evaluates the field under every foot in every
+ * substep.  terrain_height takes device pointers (env_index_dev[n], xy_dev[n][2], out_dev[n]) and
+ * launches a small kernel on the context's stream; an env index outside [0, n_envs) gives NaN. */
+int ddrl_devenv_set_terrain(ddrl_devenv* env, double lo, double hi, double bump_scale, uint32_t generation);
+int ddrl_devenv_terrain(ddrl_devenv* env, double* lo, double* hi, double* bump_scale, uint32_t* generation);
+int ddrl_devenv_new_terrain(ddrl_devenv* env);
+int ddrl_devenv_terrain_height(ddrl_devenv* env, const int32_t* env_index_dev, const double* xy_dev, int n,
+                               double* out_dev);
 /* A fragment over the device env plane, one in-order chain on the context's stream with no
  * host wait: if reset, ddrl_devenv_reset and observe(env.obs); then for t in [0, T): act(t) ->
  * devenv_step -> reward(t, env.fw, env.cfrc, actions, env.done) -> observe(env.obs); then the
  * bootstrap.  eps_dev[T][N][n_agents][A].  The loop is captured once per (env, eps_dev, env
- * settings) into a HIP graph and replayed (DDRL_ROLLOUT_GRAPH=0 at context creation issues the
+ * settings: time limit, velocity list, and the terrain settings while the ground is not flat --
+ * a set_terrain or new_terrain between two fragments re-captures) into a HIP graph and replayed (DDRL_ROLLOUT_GRAPH=0 at context creation issues the
  * launches directly); any model kind. */
 int ddrl_rollout_devenv(ddrl_ctx* ctx, ddrl_devenv* env, const float* eps_dev, int reset);
 

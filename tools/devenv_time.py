@@ -12,6 +12,15 @@ variants alternating; medians and spreads are reported.
             (8 groups, 16 host threads) and ddrl_rollout_fragment over synthetic buffers (host
             clock around call + synchronize), in env-steps/s
 Writes one JSON document (default profiles/devenv/devenv_time.json).
+
+  --terrain  the cost of uneven ground (profiles/devenv/terrain_time.json): the step launch at
+            N = 128 and 4096 and the T = 200 fragment at 4096 envs, flat and with smoothness 0.6
+            (the fragment also with a new_terrain before every call, which captures the loop
+            again), the variants alternating inside a process.  With --parent-root DIR (a built
+            checkout of the parent commit) the same flat figures are taken from that tree too, in
+            child processes of this one that alternate with this tree's, `--rounds` times each;
+            the verdict says whether this tree's flat medians lie inside the parent's
+            run-to-run spread (min .. max over its rounds).
 """
 import argparse
 import json
@@ -23,7 +32,10 @@ import time
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# --root DIR: the tree whose ddrl_amd package (and library) is measured; this one by default
+ROOT = sys.argv[sys.argv.index("--root") + 1] if "--root" in sys.argv else HERE
+sys.path.insert(0, os.path.abspath(ROOT))
 from ddrl_amd import native as N
 from ddrl_amd.spec import make_cfg
 
@@ -177,8 +189,116 @@ def time_fragments(n, T, groups, threads, repeats):
             **verdict(res), "us_per_step": us, "device_minus_synthetic_us_per_step": us["device"] - us["synthetic"]}
 
 
+SMOOTH = 0.6
+
+
+def time_terrain_step(n, steps, repeats):
+    """The step launch, flat and on uneven ground (the envs spread over x = 5 .. 45 m, off the start
+    patch); a tree without terrain gives the flat figure only."""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(3)
+    actions = torch.rand((K, n, 8), device="cuda", generator=g) * 2 - 1
+    ctx, cfg = make(n, 8)
+    env = N.DevEnv(ctx, seed=1)
+    env.reset()
+    st = env.state()
+    st[:, 0] = np.linspace(5.0, 45.0, n)
+    env.set_state(st)
+    variants = ["flat"] + (["terrain"] if hasattr(env, "set_terrain") else [])
+
+    def run(name):
+        if len(variants) > 1:
+            env.set_terrain(SMOOTH if name == "terrain" else 1.0)
+        return window(lambda i: env.step(actions[i % K]), steps)
+    res = alternate(variants, run, repeats)
+    env.close()
+    ctx.close()
+    return {"unit": "microseconds per launch", **res}
+
+
+def time_terrain_fragment(n, T, repeats):
+    g = torch.Generator(device="cuda")
+    g.manual_seed(9)
+    ctx, cfg = make(n, T)
+    eps = torch.randn((T, n, cfg.n_agents, cfg.act_dim), device="cuda", generator=g)
+    env = N.DevEnv(ctx, seed=1)
+    ctx.rollout_devenv(env, eps, reset=True)
+    has = hasattr(env, "set_terrain")
+    variants = ["flat"] + (["terrain", "terrain_renewed"] if has else [])
+
+    def run(name):
+        if has:
+            env.set_terrain(SMOOTH if name != "flat" else 1.0)
+            ctx.rollout_devenv(env, eps)      # the capture of this variant's loop is not in the window
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if name == "terrain_renewed":
+            env.new_terrain()                 # what update_environment_after_epoch does: the loop is captured again
+        ctx.rollout_devenv(env, eps)
+        ctx.synchronize()
+        return 1e6 * (time.perf_counter() - t0) / T
+    res = alternate(variants, run, repeats)
+    env.close()
+    ctx.close()
+    return {"n_envs": n, "T": T, "unit": "microseconds per env-step of the fragment (all N envs)", **res}
+
+
+def terrain_worker(a):
+    return {"step": {str(n): time_terrain_step(n, a.steps, a.repeats) for n in (128, 4096)},
+            "fragment": time_terrain_fragment(4096, 200, a.repeats)}
+
+
+def terrain_main(a):
+    """This tree and, with --parent-root, the parent's, alternating in child processes."""
+    import subprocess
+    trees = {"this": HERE}
+    if a.parent_root:
+        trees["parent"] = os.path.abspath(a.parent_root)
+    rounds = {name: [] for name in trees}
+    device = ""
+    for _ in range(a.rounds):
+        for name, root in trees.items():
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--terrain-worker", "--root", root,
+                                  "--steps", str(a.steps), "--repeats", str(a.repeats)],
+                                 capture_output=True, text=True, timeout=600)
+            if out.returncode != 0:
+                sys.exit(f"devenv_time: the {name} tree's worker failed:\n{out.stderr[-2000:]}")
+            doc = json.loads(out.stdout.strip().splitlines()[-1])
+            device = doc.pop("device")
+            rounds[name].append(doc)
+            print(name, json.dumps(doc), flush=True)
+
+    def node(doc, path):
+        for k in path:
+            doc = doc[k]
+        return doc
+
+    def medians(name, *path):
+        return [node(doc, path)["median"] for doc in rounds[name]]
+    keys = [("step", "128"), ("step", "4096"), ("fragment",)]
+    res = {"device": device, "commit": a.commit, "env": ENV, "smoothness": SMOOTH, "steps_per_window": a.steps,
+           "repeats_per_process": a.repeats, "processes_per_tree": a.rounds, "rounds": rounds, "summary": {}}
+    for path in keys:
+        first = node(rounds["this"][0], path)
+        entry = {v: summary(medians("this", *path, v)) for v in first if isinstance(first[v], dict)}
+        if "terrain" in entry:
+            entry["terrain_minus_flat"] = entry["terrain"]["median"] - entry["flat"]["median"]
+        if "parent" in rounds:
+            par = summary(medians("parent", *path, "flat"))
+            entry["parent_flat"] = par
+            entry["flat_within_parent_spread"] = bool(par["min"] <= entry["flat"]["median"] <= par["max"])
+            entry["flat_minus_parent_flat"] = entry["flat"]["median"] - par["median"]
+        res["summary"]["_".join(path)] = entry
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--root", default=HERE, help="the tree whose package is measured")
+    ap.add_argument("--terrain", action="store_true", help="the terrain case only (see the module docstring)")
+    ap.add_argument("--terrain-worker", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--parent-root", default="", help="--terrain: a built checkout of the parent commit")
+    ap.add_argument("--rounds", type=int, default=3, help="--terrain: processes per tree")
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--commit", default="")
@@ -187,6 +307,17 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("devenv_time: needs a GPU (no timing without one)")
+    if a.terrain_worker:
+        print(json.dumps({"device": torch.cuda.get_device_name(0), **terrain_worker(a)}))
+        return
+    if a.terrain:
+        res = terrain_main(a)
+        out = a.out if "--out" in sys.argv else os.path.join(HERE, "profiles", "devenv", "terrain_time.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res["summary"]))
+        return
     res = {"device": torch.cuda.get_device_name(0), "commit": a.commit, "env": ENV, "steps_per_window": a.steps,
            "repeats": a.repeats,
            "step": {str(n): time_step(n, a.steps, a.repeats) for n in (128, 4096)},
