@@ -478,7 +478,16 @@ __device__ __forceinline__ void store_act_fm(float* buf, int tile, const floatx4
 }
 
 // NT_ tiles dW[f = 16 fa_i + 4q + r][o = 16 fo + c] (one fo, NT_ fa's) over NROWS rows.
-template <int NROWS, int NT_, int LD = NROWS + 8>
+// AHEAD: the operand loads of row group u + 1 are dealt over the first three v sub-steps of
+// group u, each deal a scheduling region of its own in front of that sub-step's MFMAs, so they
+// are in flight under the group's MFMAs and waited for with a counted lgkmcnt; the MFMAs walk v
+// outer, tile inner, one region per v, so consecutive MFMAs go to different accumulators
+// (40-cycle dependent latency against 32 cycles of issue).  !AHEAD: the loads share one region
+// with group u's MFMAs; the scheduler sinks them behind the MFMAs and waits for them at once,
+// which a single wave per SIMD cannot hide -- kept for the KSP = 1 kernels, which spill more with
+// the loads held in flight.  Either way every accumulator receives its products in the same
+// (u, v) order: the same bits (profiles/dw_streams).
+template <int NROWS, int NT_, int LD = NROWS + 8, bool AHEAD = true>
 __device__ __forceinline__ void dw_tiles_fm(const float* A, const float* B, const int* fa, int fo, floatx4* out) {
   const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
 #pragma unroll
@@ -487,24 +496,48 @@ __device__ __forceinline__ void dw_tiles_fm(const float* A, const float* B, cons
   const float* ap[NT_];
 #pragma unroll
   for (int i = 0; i < NT_; ++i) ap[i] = A + (16 * fa[i] + c) * LD + 4 * q;
-  // operands of row group u + 1 are loaded while the MFMAs of group u issue
   constexpr int NU = NROWS / 16;
   floatx4 bv[2], av[2][NT_];
-  bv[0] = *reinterpret_cast<const floatx4*>(bp);
+  if constexpr (!AHEAD) {
+    bv[0] = *reinterpret_cast<const floatx4*>(bp);
 #pragma unroll
-  for (int i = 0; i < NT_; ++i) av[0][i] = *reinterpret_cast<const floatx4*>(ap[i]);
+    for (int i = 0; i < NT_; ++i) av[0][i] = *reinterpret_cast<const floatx4*>(ap[i]);
 #pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    if (u + 1 < NU) {
-      bv[(u + 1) & 1] = *reinterpret_cast<const floatx4*>(bp + 16 * (u + 1));
+    for (int u = 0; u < NU; ++u) {
+      if (u + 1 < NU) {
+        bv[(u + 1) & 1] = *reinterpret_cast<const floatx4*>(bp + 16 * (u + 1));
 #pragma unroll
-      for (int i = 0; i < NT_; ++i) av[(u + 1) & 1][i] = *reinterpret_cast<const floatx4*>(ap[i] + 16 * (u + 1));
+        for (int i = 0; i < NT_; ++i) av[(u + 1) & 1][i] = *reinterpret_cast<const floatx4*>(ap[i] + 16 * (u + 1));
+      }
+#pragma unroll
+      for (int i = 0; i < NT_; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) out[i] = mfma4(av[u & 1][i][v], bv[u & 1][v], out[i]);
+      __builtin_amdgcn_sched_barrier(0);
     }
+  } else {
+    auto ld = [&](int u, int j) {   // load j of group u
+      if (j < NT_) av[u & 1][j] = *reinterpret_cast<const floatx4*>(ap[j] + 16 * u);
+      else bv[u & 1] = *reinterpret_cast<const floatx4*>(bp + 16 * u);
+    };
+    constexpr int NL = NT_ + 1, PER = (NL + 2) / 3;
 #pragma unroll
-    for (int i = 0; i < NT_; ++i)
+    for (int j = 0; j < NL; ++j) ld(0, j);
 #pragma unroll
-      for (int v = 0; v < 4; ++v) out[i] = mfma4(av[u & 1][i][v], bv[u & 1][v], out[i]);
-    __builtin_amdgcn_sched_barrier(0);
+    for (int u = 0; u < NU; ++u) {
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        if (u + 1 < NU && v < 3) {
+#pragma unroll
+          for (int j = v * PER; j < (v + 1) * PER && j < NL; ++j) ld(u + 1, j);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int i = 0; i < NT_; ++i) out[i] = mfma4(av[u & 1][i][v], bv[u & 1][v], out[i]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
   }
 }
 

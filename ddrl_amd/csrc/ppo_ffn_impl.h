@@ -786,6 +786,8 @@ __device__ __forceinline__ void head_bwd_mfma(const NetLds& W, const float* dout
 // dw_tiles_fm plus one more tile from a second pair of images, interleaved into the same
 // MFMA stream (the policy head's dWo = H2^T dout tile of feature block fah, dout image
 // rows >= 2A zero): out[i] as dw_tiles_fm, outh[r] = dWo[16 fah + 4q + r][o = c].
+// Only the row split (KSP = 2) runs the head on MFMA, so this helper has the loads-ahead form of
+// dw_tiles_fm (common.h) alone.
 template <int NROWS, int NT_, int LD = NROWS + 8>
 __device__ __forceinline__ void dw_tiles_fm_head(const float* A, const float* B, const int* fa, int fo, floatx4* out,
                                                  const float* AH, const float* BH, int fah, floatx4& outh) {
@@ -801,27 +803,30 @@ __device__ __forceinline__ void dw_tiles_fm_head(const float* A, const float* B,
   for (int i = 0; i < NT_; ++i) ap[i] = A + (16 * fa[i] + c) * LD + 4 * q;
   constexpr int NU = NROWS / 16;
   floatx4 bv[2], av[2][NT_], bhv[2], ahv[2];
-  bv[0] = *reinterpret_cast<const floatx4*>(bp);
-  bhv[0] = *reinterpret_cast<const floatx4*>(bph);
-  ahv[0] = *reinterpret_cast<const floatx4*>(aph);
+  auto ld = [&](int u, int j) {   // load j of group u
+    if (j < NT_) av[u & 1][j] = *reinterpret_cast<const floatx4*>(ap[j] + 16 * u);
+    else if (j == NT_) bv[u & 1] = *reinterpret_cast<const floatx4*>(bp + 16 * u);
+    else if (j == NT_ + 1) ahv[u & 1] = *reinterpret_cast<const floatx4*>(aph + 16 * u);
+    else bhv[u & 1] = *reinterpret_cast<const floatx4*>(bph + 16 * u);
+  };
+  constexpr int NL = NT_ + 3, PER = (NL + 2) / 3;
 #pragma unroll
-  for (int i = 0; i < NT_; ++i) av[0][i] = *reinterpret_cast<const floatx4*>(ap[i]);
+  for (int j = 0; j < NL; ++j) ld(0, j);
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
-    if (u + 1 < NU) {
-      bv[(u + 1) & 1] = *reinterpret_cast<const floatx4*>(bp + 16 * (u + 1));
-      bhv[(u + 1) & 1] = *reinterpret_cast<const floatx4*>(bph + 16 * (u + 1));
-      ahv[(u + 1) & 1] = *reinterpret_cast<const floatx4*>(aph + 16 * (u + 1));
-#pragma unroll
-      for (int i = 0; i < NT_; ++i) av[(u + 1) & 1][i] = *reinterpret_cast<const floatx4*>(ap[i] + 16 * (u + 1));
-    }
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
+      if (u + 1 < NU && v < 3) {
+#pragma unroll
+        for (int j = v * PER; j < (v + 1) * PER && j < NL; ++j) ld(u + 1, j);
+        __builtin_amdgcn_sched_barrier(0);
+      }
 #pragma unroll
       for (int i = 0; i < NT_; ++i) out[i] = mfma4(av[u & 1][i][v], bv[u & 1][v], out[i]);
       outh = mfma4(ahv[u & 1][v], bhv[u & 1][v], outh);
+      __builtin_amdgcn_sched_barrier(0);
     }
-    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -830,6 +835,8 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
   constexpr int ROWS = DDRL_MB / KSP;
   constexpr int NT = Geo<NW, ROWS>::NT, RT = Geo<NW, ROWS>::RT, NS1 = Geo<NW, ROWS>::NS1, NS2 = Geo<NW, ROWS>::NS2;
   constexpr bool PAD = update_pad(A, KSP);   // layout of the weight images (common.h)
+  // the data-parallel gradient launches keep the dW loads sunk: they spill more with them ahead
+  constexpr bool DWF = KSP != 1;
   const int wkq = ub.own_kq < 0 ? 0 : ub.own_kq;   // the half that writes back and writes the statistics
   const UpdateHyper& H = ub.h;
   const int d = U.d;
@@ -1175,13 +1182,14 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
 #ifndef DDRL_ABL_NO_DW2   // ablation builds (timing only): skip a phase
     if constexpr (HMF) {
       static_assert(NW == 4, "one head tile (16 features) per wave");
+      static_assert(DWF, "the head tile's helper has the loads-ahead form only");
       floatx4 gh;
       dw_tiles_fm_head<ROWS, NS1, ROWS + 8>(bufA, bufB, tfa, w & 3, gt, bufH, bufD, w, gh);   // dW2 tiles + dWo
       if (c < OB)
 #pragma unroll
         for (int r = 0; r < 4; ++r) Pb[(16 * w + 4 * q + r) * OB + c] = gh[r];
     } else {
-      dw_tiles_fm<ROWS, NS1, ROWS + 8>(bufA, bufB, tfa, w & 3, gt);   // dW2 tiles of this wave
+      dw_tiles_fm<ROWS, NS1, ROWS + 8, DWF>(bufA, bufB, tfa, w & 3, gt);   // dW2 tiles of this wave
     }
 #else
     for (int i = 0; i < NS1; ++i) gt[i] = splat4(0.f);
@@ -1239,11 +1247,11 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
 #ifdef DDRL_ABL_NO_DW1
       n1 = -1;
 #endif
-      if (n1 == NS2) dw_tiles_fm<ROWS, NS2, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+      if (n1 == NS2) dw_tiles_fm<ROWS, NS2, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
       else if constexpr (NS2 >= 3) {
-        if (n1 == 2) dw_tiles_fm<ROWS, 2, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
-        else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
-      } else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+        if (n1 == 2) dw_tiles_fm<ROWS, 2, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+        else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+      } else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
     }
     STAMP(10);
     if constexpr (KSP == 2) {

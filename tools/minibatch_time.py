@@ -8,16 +8,20 @@ Three variants per shape, each with a context of its own over the same seeded ro
               libddrl_hip.so, built from its tree and copied next to this one; default
               ddrl_amd/libddrl_hip_parent.so) -- the 128 figure the comparison uses,
   new128      the same in this tree's library (no 128 code changed: it must agree),
-  new256      sgd_minibatch_size 256 in this tree's library.
+  new256      sgd_minibatch_size 256 in this tree's library,
+  parent256   (--parent-256) sgd_minibatch_size 256 in the parent commit's library: the A/B of a
+              change to the 256-row kernels themselves.
 Device events around whole launches (ddrl_ppo_update of the full 10-epoch schedule), one
 warm-up launch per variant, then --repeats launches per variant with the variants alternating;
 every launch starts from the same weights and Adam state.  Reported: the median and the spread
-in microseconds per step, rows per microsecond, and the cost of one 256-row step against two
-128-row steps of the parent library.  Writes profiles/minibatch/minibatch_time.json.
+in microseconds per step, rows per microsecond, the SHA-256 of theta after the last launch (equal
+between variants of one size that claim the same arithmetic), and the cost of one 256-row step
+against two 128-row steps of the parent library.  Writes profiles/minibatch/minibatch_time.json.
 
-    python tools/minibatch_time.py [--repeats 5] [--parent-lib PATH | --no-parent]
+    python tools/minibatch_time.py [--repeats 5] [--parent-lib PATH | --no-parent] [--parent-256]
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -95,7 +99,9 @@ def time_shape(env, n, repeats, libs):
         med = statistics.median(t[name])
         out[name] = {"sgd_minibatch_size": v.mb, "steps_per_launch": v.steps, "median_us_per_step": med,
                      "min_us_per_step": min(t[name]), "max_us_per_step": max(t[name]),
-                     "rows_per_us": v.mb / med, "launch_ms": med * v.steps * 1e-3}
+                     "us_per_step": t[name], "rows_per_us": v.mb / med, "launch_ms": med * v.steps * 1e-3,
+                     "theta_sha256": hashlib.sha256(b"".join(v.ctx.params_get(p).tobytes()
+                                                             for p in range(v.P))).hexdigest()[:16]}
         v.ctx.close()
     base = out.get("parent128", out["new128"])
     out["base_128"] = "parent128" if "parent128" in out else "new128"
@@ -110,6 +116,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--parent-lib", default=os.path.join(os.path.dirname(N.LIB_PATH), "libddrl_hip_parent.so"))
     ap.add_argument("--no-parent", action="store_true", help="compare against this tree's 128-row kernels only")
+    ap.add_argument("--parent-256", action="store_true", help="also time the parent library's 256-row step")
     ap.add_argument("--commit", default="")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "minibatch", "minibatch_time.json"))
     a = ap.parse_args()
@@ -123,6 +130,8 @@ def main():
         libs["parent128"] = (a.parent_lib, 128)
     libs["new128"] = (N.LIB_PATH, 128)
     libs["new256"] = (N.LIB_PATH, 256)
+    if a.parent_256 and not a.no_parent:
+        libs["parent256"] = (a.parent_lib, 256)
     res = {"device": torch.cuda.get_device_name(0), "commit": a.commit, "frag_len": T, "repeats": a.repeats,
            "unit": "microseconds per minibatch step (all policies of the launch side by side), device events "
                    "around whole 10-epoch launches, variants alternating",
