@@ -128,6 +128,16 @@ struct ddrl_ctx {
   float* ev_kin = nullptr;
   int ev_table_E = 0;
   int ev_normc_ok = 0;
+  // evaluation members (ddrl_eval_members_*): mem_on = M while the mode is on, member m owns the
+  // envs [m n, (m + 1) n).  Per member: the flat parameters of every policy (mem_theta[p], stride
+  // mem_tstride[p] floats), the env-side filter block (FM_* layout), the per-policy filter state
+  // [P][PF_STRIDE] and the chunk scratch of the filter push.  mem_cap: the M the buffers hold;
+  // mem_normc_ok: every member's filter constants are current
+  int mem_on = 0, mem_cap = 0, mem_normc_ok = 0;
+  float* mem_theta[DDRL_MAXP] = {nullptr};
+  size_t mem_tstride[DDRL_MAXP] = {0};
+  double *mem_filt = nullptr, *mem_pf = nullptr, *mem_part = nullptr;
+  std::vector<char> mem_loaded;
   // input sensitivity (ddrl_eval_sens_*): the steps [P][DDRL_MAXD], per policy the per-base-row
   // accumulators [C][2][d][A] and step counts [C], the reduced result; sens_act_ok: a
   // ddrl_eval_act has run since the filter constants may last have changed
@@ -165,6 +175,7 @@ struct ddrl_devenv {
   std::vector<double> tv_list;
   double* tv_dev = nullptr;
   size_t tv_cap = 0;
+  double* tv_env_dev = nullptr;   // [N] per-env velocities (set_env_target_velocities), allocated on first use
   double* packed = nullptr;
   std::vector<void*> allocs;
 };
@@ -1044,13 +1055,127 @@ int ddrl_eval_begin(ddrl_ctx* c, const ddrl_eval_cfg* ec) {
   c->ev_normc_ok = 0;
   c->sens_on = 0;
   c->sens_act_ok = 0;
+  c->mem_on = 0;
   c->ev_on = 1;
+  return 0;
+}
+
+// ---- evaluation members (eval_members.hip) -------------------------------------------------
+int ddrl_eval_members_begin(ddrl_ctx* c, int n_members) {
+  CHK_EVAL(c);
+  const ddrl_cfg& g = c->cfg;
+  if (n_members < 1) return fail("evaluation members: n_members must be >= 1");
+  if (g.n_envs % n_members) return fail("evaluation members: n_members must divide n_envs");
+  if (c->sens_on) return fail("evaluation members: the sensitivity mode is on (sensitivity per member is not supported)");
+  const int M = n_members, n = g.n_envs / M;
+  HIPCHK(hipStreamSynchronize(c->stream));   // nothing in flight reads a buffer that is replaced
+  c->mem_on = 0;
+  if (M > c->mem_cap) {
+    for (int p = 0; p < g.n_policies; ++p) dfree(c, &c->mem_theta[p]);
+    dfree(c, &c->mem_filt);
+    dfree(c, &c->mem_pf);
+    c->mem_cap = 0;
+    for (int p = 0; p < g.n_policies; ++p) {
+      c->mem_tstride[p] = ((size_t)c->pol[p].n_params + 3) & ~(size_t)3;
+      if (dalloc(c, &c->mem_theta[p], (size_t)M * c->mem_tstride[p])) return -1;
+    }
+    if (dalloc(c, &c->mem_filt, (size_t)M * FM_STRIDE) ||
+        dalloc(c, &c->mem_pf, (size_t)M * g.n_policies * PF_STRIDE))
+      return -1;
+    c->mem_cap = M;
+  }
+  // the chunk scratch depends on n as well: M * filter_part_doubles(n) is largest at the smallest M
+  dfree(c, &c->mem_part);
+  if (dalloc(c, &c->mem_part, (size_t)M * filter_part_doubles(n, DDRL_MAXFULL))) return -1;
+  c->mem_loaded.assign(M, 0);
+  c->mem_normc_ok = 0;
+  c->mem_on = M;
+  return 0;
+}
+
+#define CHK_MEMBER(c, m)                                                                    \
+  do {                                                                                      \
+    CHK_EVAL(c);                                                                            \
+    if (!(c)->mem_on) return fail("evaluation members: call ddrl_eval_members_begin first"); \
+    if ((m) < 0 || (m) >= (c)->mem_on)                                                      \
+      return fail("evaluation members: member " + std::to_string(m) + " is out of range [0, " + \
+                  std::to_string((c)->mem_on) + ")");                                       \
+  } while (0)
+
+int ddrl_eval_member_load(ddrl_ctx* c, int member) {
+  CHK_MEMBER(c, member);
+  const ddrl_cfg& g = c->cfg;
+  const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+  for (int p = 0; p < g.n_policies; ++p)
+    HIPCHK(hipMemcpyAsync(c->mem_theta[p] + (size_t)member * c->mem_tstride[p], c->pol[p].theta,
+                          (size_t)c->pol[p].n_params * 4, dd, c->stream));
+  double* F = c->mem_filt + (size_t)member * FM_STRIDE;
+  HIPCHK(hipMemcpyAsync(F + FM_N, c->f_n, 8, dd, c->stream));
+  HIPCHK(hipMemcpyAsync(F + FM_M, c->f_M, DDRL_MAXFULL * 8, dd, c->stream));
+  HIPCHK(hipMemcpyAsync(F + FM_S, c->f_S, DDRL_MAXFULL * 8, dd, c->stream));
+  HIPCHK(hipMemsetAsync(F + FM_DN, 0, (1 + 2 * DDRL_MAXFULL) * 8, c->stream));   // the delta stat starts empty
+  if (g.policy_filter) {
+    // the constants ddrl_eval_act would use now: the read-only pass rewrites them from (n, M, S)
+    launch_policy_filter(c->stream, c->route, nullptr, c->f_normc, 0.f, c->zs, c->pf, 0);
+    HIPCHK(hipGetLastError());
+    const size_t n = (size_t)g.n_policies * PF_STRIDE;
+    HIPCHK(hipMemcpyAsync(c->mem_pf + (size_t)member * n, c->pf, n * 8, dd, c->stream));
+  }
+  c->mem_loaded[member] = 1;
+  c->mem_normc_ok = 0;
+  return 0;
+}
+
+int ddrl_eval_member_filter_get(ddrl_ctx* c, int member, double* n, double* M, double* S) {
+  CHK_MEMBER(c, member);
+  if (!n || !M || !S) return fail("null filter buffer");
+  const int D = c->cfg.obs_full_dim;
+  const double* F = c->mem_filt + (size_t)member * FM_STRIDE;
+  HIPCHK(hipMemcpyAsync(n, F + FM_N, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(M, F + FM_M, D * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(S, F + FM_S, D * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ddrl_eval_act with the member mode on: member state only, the context's own is not touched
+static int eval_act_members(ddrl_ctx* c, const float* obs, const float* eps, float* actions,
+                            float* const* logits_out) {
+  const ddrl_cfg& g = c->cfg;
+  const int M = c->mem_on, n = g.n_envs / M;
+  for (int m = 0; m < M; ++m)
+    if (!c->mem_loaded[m]) return fail("evaluation members: member " + std::to_string(m) + " has not been loaded");
+  const int push = g.filter_enabled && c->ev_cfg.filter_update;
+  // a frozen filter's constants are written once per members_begin / member_load
+  if (push || !c->mem_normc_ok) {
+    launch_filter_push_members(c->stream, obs, n, g.obs_full_dim, M, c->mem_filt, c->ev_cfg.filter_update,
+                               g.filter_enabled, c->mem_part);
+    c->mem_normc_ok = !push;
+  }
+  EvalMembersArgs ma{};
+  for (int p = 0; p < g.n_policies; ++p) {
+    ma.theta[p] = c->mem_theta[p];
+    ma.theta_stride[p] = c->mem_tstride[p];
+    ma.cup_off[p] = g.leg_coupling ? ffn_param_count(c->pol[p].d, g.act_dim) : -1;
+    ma.logits_out[p] = logits_out ? logits_out[p] : nullptr;
+  }
+  ma.obs = obs; ma.filt = c->mem_filt;
+  ma.pf = g.policy_filter ? c->mem_pf : nullptr;
+  ma.pf_stride = (size_t)g.n_policies * PF_STRIDE;
+  ma.clip = effective_clip(g);
+  ma.eps = eps; ma.actions = actions;
+  RouteArgs ra = c->route;
+  ra.e0 = 0;
+  ra.N = n;
+  launch_eval_act_members(c->stream, ra, ma, M);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 
 int ddrl_eval_act(ddrl_ctx* c, const float* obs, const float* eps, float* actions, float* const* logits_out) {
   CHK_EVAL(c);
   if (!obs || !actions) return fail("null observation / actions buffer");
+  if (c->mem_on) return eval_act_members(c, obs, eps, actions, logits_out);
   const ddrl_cfg& g = c->cfg;
   const int N = g.n_envs;
   const int push = g.filter_enabled && c->ev_cfg.filter_update;
@@ -1119,6 +1244,7 @@ int ddrl_eval_end(ddrl_ctx* c) {
   HIPCHK(hipStreamSynchronize(c->stream));
   c->ev_on = 0;
   c->sens_on = 0;
+  c->mem_on = 0;
   return 0;
 }
 
@@ -1126,6 +1252,7 @@ int ddrl_eval_end(ddrl_ctx* c) {
 int ddrl_eval_sens_begin(ddrl_ctx* c, const double* const* step_host) {
   CHK_EVAL(c);
   if (c->cfg.model_kind != DDRL_MODEL_FFN) return fail("sensitivity: fcnet models only");
+  if (c->mem_on) return fail("sensitivity: the evaluation member mode is on (sensitivity per member is not supported)");
   if (!step_host) return fail("sensitivity: null step array");
   const ddrl_cfg& g = c->cfg;
   std::vector<double> steps((size_t)DDRL_MAXP * DDRL_MAXD, 0.0);
@@ -1212,6 +1339,9 @@ int ddrl_eval_hostenv(ddrl_ctx* c, ddrl_hostenv* env, const float* eps_dev, int 
   CHK_EVAL(c);
   const ddrl_cfg& g = c->cfg;
   if (!env) return fail("null host env");
+  if (c->mem_on)
+    return fail("evaluation: the member mode is on and the host env plane has no per-env target velocity "
+                "(use the device env plane)");
   if (env->N != g.n_envs || env->D != g.obs_full_dim) return fail("host env shape differs from the context's");
   if (max_steps < 1 || poll_every < 1) return fail("evaluation: max_steps and poll_every must be >= 1");
   if (eps_dev && eps_steps < 1) return fail("evaluation: eps_steps must be >= 1 with a noise buffer");
@@ -1364,6 +1494,33 @@ int ddrl_devenv_set_target_velocities(ddrl_devenv* e, const float* list, int n) 
   HIPCHK(hipMemcpy(e->tv_dev, e->tv_list.data(), (size_t)n * 8, hipMemcpyHostToDevice));
   e->a.tv_list = e->tv_dev;
   e->a.n_tv = n;
+  ++e->gen;
+  return 0;
+}
+
+int ddrl_devenv_set_env_target_velocities(ddrl_devenv* e, const float* per_env, int n_envs) {
+  CHK_ENV(e);
+  if (per_env) {
+    if (n_envs != e->a.N) return fail("ddrl_devenv_set_env_target_velocities: per_env holds n_envs floats");
+    for (int i = 0; i < n_envs; ++i) {
+      if (!std::isfinite(per_env[i]))
+        return fail("ddrl_devenv_set_env_target_velocities: target velocities must be finite");
+      if (e->a.D > 43 && !(per_env[i] > 0.f))
+        return fail("ddrl_devenv_set_env_target_velocities: obs_dim 44 needs target velocities > 0 "
+                    "(the TVel reward divides by it)");
+    }
+  }
+  // launches in flight still read the old table
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));
+  if (per_env) {
+    if (!e->tv_env_dev && !env_alloc(e, &e->tv_env_dev, (size_t)e->a.N))
+      return fail("ddrl_devenv_set_env_target_velocities: device buffer allocation failed");
+    const std::vector<double> tv(per_env, per_env + n_envs);
+    HIPCHK(hipMemcpy(e->tv_env_dev, tv.data(), (size_t)n_envs * 8, hipMemcpyHostToDevice));
+    e->a.tv_env = e->tv_env_dev;
+  } else {
+    e->a.tv_env = nullptr;
+  }
   ++e->gen;
   return 0;
 }

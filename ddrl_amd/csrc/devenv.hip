@@ -64,7 +64,12 @@ __device__ __forceinline__ double quad_get(double v) { return dpp_mov_d<K * 0x55
 // integer and fp64 ALU work, no memory traffic) ahead of its contact force; what does not depend
 // on the point (the field's hash key, the env's smoothness) is formed once per step.  The flat
 // instance contains none of it.
-template <bool kTerrain>
+//
+// kTvEnv: the instance for a per-env velocity table (DevEnvArgs::tv_env): a restarting env takes
+// its own entry instead of a draw from the list.  An instance and not a test of the pointer: with
+// the test in it the flat kernel measured 0.24 us longer per launch than without
+// (profiles/eval/sweep_time.json, DESIGN.md section 3 "Evaluation members").
+template <bool kTerrain, bool kTvEnv>
 __global__ void __launch_bounds__(256) k_devenv_step(DevEnvArgs A, const float* __restrict__ actions) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   const int e = g >> 2, leg = g & 3;
@@ -136,7 +141,8 @@ __global__ void __launch_bounds__(256) k_devenv_step(DevEnvArgs A, const float* 
   if (d) {
     episode += 1;
     steps = 0;
-    tv = draw_tv(A.seed, e, episode, A.tv_list, A.n_tv);
+    if constexpr (kTvEnv) tv = A.tv_env[e];
+    else tv = draw_tv(A.seed, e, episode, A.tv_list, A.n_tv);
     t = Torso{0.0, 0.0, reset_z(A.seed, e, episode), 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     q_h = reset_q(A.seed, e, episode, hip); q_k = reset_q(A.seed, e, episode, knee);
     qd_h = reset_qd(A.seed, e, episode, hip); qd_k = reset_qd(A.seed, e, episode, knee);
@@ -191,6 +197,7 @@ __global__ void __launch_bounds__(64) k_devenv_reset(DevEnvArgs A, int mode) {
   EnvState s = load_state(A, e);
   if (mode == DEVENV_RESET_ALL) s.episode = 0;
   reset_env(s, A.seed, e, mode != DEVENV_RESET_STATE, A.tv_list, A.n_tv);
+  if (A.tv_env && mode != DEVENV_RESET_STATE) s.tv = A.tv_env[e];   // the env's fixed velocity, not the draw
   if (mode == DEVENV_RESET_ALL) s.steps = stagger_steps(A.seed, e, A.time_limit);
   if (mode != DEVENV_RESET_STATE) {
     write_obs(s, A.obs + (size_t)e * A.D, A.D, nullptr);
@@ -229,8 +236,14 @@ __global__ void __launch_bounds__(64) k_devenv_terrain_height(DevEnvArgs A, cons
 }  // namespace
 
 void launch_devenv_step(hipStream_t s, const DevEnvArgs& a, const float* actions) {
-  if (a.ter_on) hipLaunchKernelGGL(k_devenv_step<true>, dim3((4 * a.N + 255) / 256), dim3(256), 0, s, a, actions);
-  else hipLaunchKernelGGL(k_devenv_step<false>, dim3((4 * a.N + 255) / 256), dim3(256), 0, s, a, actions);
+  const dim3 grid((4 * a.N + 255) / 256);
+  if (a.tv_env) {
+    if (a.ter_on) hipLaunchKernelGGL((k_devenv_step<true, true>), grid, dim3(256), 0, s, a, actions);
+    else hipLaunchKernelGGL((k_devenv_step<false, true>), grid, dim3(256), 0, s, a, actions);
+  } else {
+    if (a.ter_on) hipLaunchKernelGGL((k_devenv_step<true, false>), grid, dim3(256), 0, s, a, actions);
+    else hipLaunchKernelGGL((k_devenv_step<false, false>), grid, dim3(256), 0, s, a, actions);
+  }
 }
 
 void launch_devenv_terrain_height(hipStream_t s, const DevEnvArgs& a, const int* env_index, const double* xy, int n,

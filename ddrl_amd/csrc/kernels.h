@@ -143,6 +143,40 @@ struct EvalAccumArgs {
 void launch_eval_accum(hipStream_t s, const RewardArgs& ra, const EvalAccumArgs& ev, const float* fw,
                        const float* cfrc, const float* actions, const float* kin, const uint8_t* done);
 
+// ---- evaluation members (eval_members.hip): M parameter sets side by side, n envs each ----
+// Member m owns the envs [m n, (m + 1) n).  Its state is addressed as base + m * stride, the
+// strides by value in the argument block (no per-member pointer table anywhere).
+// The env-side filter of a member, one block of FM_STRIDE doubles: running stat (n, M, S), the
+// delta stat (pushes since the load) and the normalization constants (mean, std + 1e-8) per column
+#define FM_N 0
+#define FM_M 1
+#define FM_S (FM_M + DDRL_MAXFULL)
+#define FM_DN (FM_S + DDRL_MAXFULL)
+#define FM_DM (FM_DN + 1)
+#define FM_DS (FM_DM + DDRL_MAXFULL)
+#define FM_NORMC (FM_DS + DDRL_MAXFULL)
+#define FM_STRIDE (FM_NORMC + 2 * DDRL_MAXFULL)
+struct EvalMembersArgs {
+  const float* theta[DDRL_MAXP];   // member 0's flat parameters of each policy (the cup table included)
+  size_t theta_stride[DDRL_MAXP];  // floats from one member's parameters to the next
+  int cup_off[DDRL_MAXP];          // offset of the "cup" table [4][A] in the parameters (< 0: none)
+  const float* obs;                // raw observations [M n][full_dim]
+  const double* filt;              // [M][FM_STRIDE]
+  const double* pf;                // [M][P][PF_STRIDE] per-policy filter state, or nullptr
+  size_t pf_stride;                // doubles per member
+  float clip;
+  float* logits_out[DDRL_MAXP];    // optional [M n k_p][2A], member-major
+  const float* eps;                // [M n][n_agents][A] or nullptr
+  float* actions;                  // [M n][8]
+};
+// ra.N = n, the envs of ONE member; grid (ceil(n k_max / 64), P, M)
+void launch_eval_act_members(hipStream_t s, const RouteArgs& ra, const EvalMembersArgs& ma, int n_members);
+// launch_filter_push with a member index in the grid: chunks counted from the member's first env,
+// merged in order; the count of a pushed batch is added by the merge kernel itself, after every
+// column has read it.  part: n_members * filter_part_doubles(n, D) doubles
+void launch_filter_push_members(hipStream_t s, const float* obs, int n, int D, int n_members, double* filt,
+                                int update, int enabled, double* part);
+
 // ---- input sensitivity of the evaluated policies (eval_sens.hip) ----
 struct EvalSensArgs {
   PolicyInputArgs in;              // normc: as the step's ddrl_eval_act read them
@@ -204,6 +238,7 @@ struct DevEnvArgs {
   int* steps;                // [N]
   unsigned* episode;         // [N]
   const double* tv_list;     // [n_tv]
+  const double* tv_env;      // [N] fixed target velocity of every env, or nullptr: drawn from tv_list
   float *obs, *fw, *cfrc, *kin;   // [N][D], [N], [N][14][6], [N][9]
   uint8_t* done;             // [N]
   // the ground (envdyn::Terrain): smoothness bounds, bump spacing and its inverse, generation;

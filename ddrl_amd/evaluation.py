@@ -98,10 +98,67 @@ def evaluate_checkpoints(config, checkpoint_paths, approach, hf_smoothness=1.0, 
     return rows
 
 
+# evaluate_trained_policies_tvel_range_pd.py:63: the same columns with target_velocity after evaluated_on
+COLUMNS_TVEL = COLUMNS[:4] + ["target_velocity"] + COLUMNS[4:]
+MAX_SWEEP_ENVS = 4096   # envs of one evaluate_members call
+
+
+def evaluate_sweep(config, checkpoint_paths, approach, target_velocities=None, hf_smoothness=1.0, num_episodes=10,
+                   num_steps=1000, seeds=None, trained_on="flat", device=0, **evaluate_args):
+    """evaluate_checkpoints' rows for a whole sweep from ONE trainer and one evaluation per batch:
+    the members are checkpoints x target velocities, checkpoint-major (the loops of
+    evaluate_trained_policies_pd.py:84-127 and evaluate_trained_policies_tvel_range_pd.py:80-102),
+    run side by side by PPOTrainer.evaluate_members on the device env plane.  The sweep is split
+    into several evaluate_members calls when members x envs per member would pass 4096 envs.
+    target_velocities None: one member per checkpoint at the configured velocity, COLUMNS rows;
+    given: every row also carries `target_velocity` (COLUMNS_TVEL).  seeds: the `seed` label of
+    each checkpoint (default: its index).  evaluate_args go to evaluate_members (explore,
+    env_filter, seed)."""
+    checkpoint_paths = list(checkpoint_paths)
+    if not checkpoint_paths:
+        raise ValueError("evaluate_sweep: no checkpoints")
+    if seeds is not None and len(seeds) != len(checkpoint_paths):
+        raise ValueError(f"evaluate_sweep: {len(seeds)} seed labels for {len(checkpoint_paths)} checkpoints")
+    num_episodes = int(num_episodes)
+    if num_episodes < 1:
+        raise ValueError("evaluate_sweep: num_episodes must be >= 1")
+    tvs = None
+    if target_velocities is not None:
+        tvs = [float(v) for v in np.asarray(target_velocities, np.float64).reshape(-1)]
+        if not tvs or not all(np.isfinite(v) and v > 0.0 for v in tvs):
+            raise ValueError("evaluate_sweep: target_velocities must be a non-empty list of finite values > 0")
+    cells = [(k, path, tv) for k, path in enumerate(checkpoint_paths) for tv in (tvs or [None])]
+    # members per call: every member keeps min(num_episodes, 4096 // M) envs, so M <= 4096 // envs wanted
+    per_call = max(1, MAX_SWEEP_ENVS // min(num_episodes, MAX_SWEEP_ENVS))
+    from .trainer import PPOTrainer
+    agent = PPOTrainer(config, n_envs=8, device=device)   # the training shard is not used: a small one
+    rows = []
+    try:
+        for i in range(0, len(cells), per_call):
+            batch = cells[i:i + per_call]
+            results = agent.evaluate_members([(path, tv) for _, path, tv in batch], num_episodes=num_episodes,
+                                             num_steps=num_steps, hf_smoothness=hf_smoothness, **evaluate_args)
+            for (k, _, tv), res in zip(batch, results):
+                seed = seeds[k] if seeds is not None else k
+                for it in range(len(res[0])):
+                    row = {"approach": approach, "seed": seed, "trained_on": trained_on,
+                           "evaluated_on": float(hf_smoothness), "simulation_run": it, "reward": res[0][it],
+                           "duration": res[1][it], "distance": res[2][it], "power": res[3][it],
+                           "velocity": res[4][it], "CoT": res[5][it]}
+                    if tvs is not None:
+                        row["target_velocity"] = tv
+                    rows.append(row)
+    finally:
+        agent.stop()
+    return rows
+
+
 def write_csv(rows, path):
-    """The rows as evaluation_<hf_smoothness>.csv (the csv module: pandas may be absent)."""
+    """The rows as evaluation_<hf_smoothness>.csv (the csv module: pandas may be absent); with the
+    target_velocity column (evaluation_tvel_range_<hf_smoothness>.csv) only when rows carry it."""
+    rows = list(rows)
     with open(path, "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=COLUMNS)
+        w = csv.DictWriter(f, fieldnames=COLUMNS_TVEL if any("target_velocity" in r for r in rows) else COLUMNS)
         w.writeheader()
         w.writerows(rows)
     return path

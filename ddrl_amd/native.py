@@ -151,6 +151,7 @@ _SIGS = {
     "ddrl_devenv_set_time_limit": ([VP, C.c_int], C.c_int),
     "ddrl_devenv_set_target_velocities": ([VP, C.POINTER(C.c_float), C.c_int], C.c_int),
     "ddrl_devenv_target_velocities": ([VP, C.POINTER(C.c_float), C.c_int], C.c_int),
+    "ddrl_devenv_set_env_target_velocities": ([VP, C.POINTER(C.c_float), C.c_int], C.c_int),
     "ddrl_devenv_step": ([VP, VP], C.c_int),
     "ddrl_devenv_state_get": ([VP, VP, C.c_size_t], C.c_int),
     "ddrl_devenv_state_set": ([VP, VP, C.c_size_t], C.c_int),
@@ -163,6 +164,9 @@ _SIGS = {
     "ddrl_eval_results": ([VP, VP, C.c_size_t], C.c_int),
     "ddrl_eval_end": ([VP], C.c_int),
     "ddrl_eval_hostenv": ([VP, VP, VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
+    "ddrl_eval_members_begin": ([VP, C.c_int], C.c_int),
+    "ddrl_eval_member_load": ([VP, C.c_int], C.c_int),
+    "ddrl_eval_member_filter_get": ([VP, C.c_int, VP, VP, VP], C.c_int),
     "ddrl_eval_sens_begin": ([VP, C.POINTER(VP)], C.c_int),
     "ddrl_eval_sens": ([VP, VP, C.POINTER(VP)], C.c_int),
     "ddrl_eval_sens_results": ([VP, C.c_int, VP, VP, C.POINTER(C.c_int64)], C.c_int),
@@ -591,6 +595,28 @@ class Context:
                                       C.byref(n)))
         return int(n.value)
 
+    # ---- evaluation members: M parameter sets side by side, n_envs / M envs each ----
+    def eval_members_begin(self, n_members):
+        """After eval_begin: member m owns the envs [m n, (m + 1) n), n = n_envs / n_members, and
+        eval_act runs every member on its own weights and filters.  All members start unloaded;
+        eval_end (or the next eval_begin) ends the mode."""
+        _ck(self.lib.ddrl_eval_members_begin(self.h, int(n_members)))
+
+    def eval_member_load(self, member):
+        """The context's current parameters, env-side filter and per-policy filters into the
+        member's slot (device-to-device, stream-ordered): set them with params_set / filter_set /
+        policy_filter_set first."""
+        _ck(self.lib.ddrl_eval_member_load(self.h, int(member)))
+
+    def eval_member_filter_get(self, member):
+        """(n, M, S) of the member's env-side running stat; synchronizes."""
+        D = self.cfg.obs_full_dim
+        n = np.zeros(1, np.float64)
+        M = np.zeros(D, np.float64)
+        S = np.zeros(D, np.float64)
+        _ck(self.lib.ddrl_eval_member_filter_get(self.h, int(member), n.ctypes.data, M.ctypes.data, S.ctypes.data))
+        return float(n[0]), M, S
+
     # ---- input sensitivity of the evaluated policies (between eval_begin and eval_end) ----
     def eval_sens_begin(self, steps):
         """steps: per policy the perturbation h_f of each env-normalized input, obs_dim[p] finite
@@ -851,6 +877,16 @@ class DevEnv:
         self._live()
         tvs = [float(v) for v in tvs]
         _ck(self.lib.ddrl_devenv_set_target_velocities(self.h, (C.c_float * len(tvs))(*tvs), len(tvs)))
+
+    def set_env_target_velocities(self, tvs):
+        """A fixed target velocity per env (n_envs values) at every reset and episode restart, or
+        None to go back to drawing from the list."""
+        self._live()
+        if tvs is None:
+            _ck(self.lib.ddrl_devenv_set_env_target_velocities(self.h, None, 0))
+            return
+        tvs = [float(v) for v in np.asarray(tvs).reshape(-1)]
+        _ck(self.lib.ddrl_devenv_set_env_target_velocities(self.h, (C.c_float * len(tvs))(*tvs), len(tvs)))
 
     def set_terrain(self, lo, hi=None, bump_scale=2.0, generation=None):
         """HostEnv.set_terrain for the device plane: holds for the launches issued after it."""

@@ -615,6 +615,118 @@ class PPOTrainer:
         reward, steps, dist, power, vel, cot = (rows[:, i].tolist() for i in range(6))
         return (reward, [int(s) for s in steps], dist, power, vel, cot), sens
 
+    def evaluate_members(self, members, num_episodes=10, num_steps=1000, explore=True, env_filter="continue", seed=0,
+                         hf_smoothness=None):
+        """evaluate() of many parameter sets side by side, the cells of the reference's sweeps
+        (evaluation/evaluate_trained_policies_pd.py:84-127, one restored agent per seed;
+        evaluate_trained_policies_tvel_range_pd.py:80-102, one per seed and target velocity) as one
+        evaluation.  members: a list of (checkpoint_path or None, tvel or None) -- None: the
+        trainer's current state, its configured velocity.  Returns one six-list tuple per member.
+
+        Always on the device env plane, on the trainer's evaluation context of M * n envs with the
+        member mode on (ddrl_eval_members_begin): n = min(num_episodes, 4096 // M) envs per member,
+        E = ceil(num_episodes / n) episodes per env, member m on the envs [m n, (m + 1) n).  Every
+        member has its own weights, per-policy filters and env-side filter (env_filter as in
+        evaluate(), applied per member: each starts from the training filter, or fresh, and keeps
+        its own statistics).  A checkpoint (an RLlib checkpoint file, read with the no-code reader)
+        is written into the evaluation context only: the training and rollout contexts, their Adam
+        state and filters are not touched.  Members whose tvel is None on a trainer with several
+        configured velocities draw from that list, as evaluate() does."""
+        members = [tuple(m) for m in members]
+        M = len(members)
+        if M < 1:
+            raise ValueError("evaluate_members: at least one member")
+        if M > 4096:
+            raise ValueError(f"evaluate_members: {M} members, at most 4096 (one env each) fit an evaluation; "
+                             "split the sweep (ddrl_amd.evaluation.evaluate_sweep does)")
+        if any(len(m) != 2 for m in members):
+            raise ValueError("evaluate_members: members are (checkpoint_path or None, tvel or None) pairs")
+        for _, tvel in members:
+            if tvel is not None and not (np.isfinite(float(tvel)) and float(tvel) > 0.0):
+                raise ValueError(f"evaluate_members: target velocity {tvel!r} must be finite and > 0")
+        if env_filter not in ("continue", "frozen", "fresh"):
+            raise ValueError(f"env_filter {env_filter!r}: 'continue', 'frozen' or 'fresh'")
+        num_episodes, num_steps = int(num_episodes), int(num_steps)
+        if num_episodes < 1 or num_steps < 1:
+            raise ValueError("num_episodes and num_steps must be >= 1")
+        if self.cfg.model_kind != N.MODEL_FFN:
+            raise N.DdrlError("evaluation: fcnet models only")
+        from .rllib_checkpoint import policy_ids, policy_state, read_checkpoint
+        torch, cfg = self.torch, self.cfg
+        n = min(num_episodes, 4096 // M)
+        E = -(-num_episodes // n)
+        n_envs = M * n
+        # the checkpoints, read and checked before anything is launched
+        states = {}
+        for path, _ in members:
+            if path is None or path in states:
+                continue
+            ck = read_checkpoint(path)
+            st = {pid: policy_state(ck, pid) for pid in policy_ids(ck)}
+            missing = [pid for pid in self.policy_ids if pid not in st]
+            if missing:
+                raise ValueError(f"{path}: checkpoint has policies {sorted(st)}, this env needs {self.policy_ids}")
+            for p, pid in enumerate(self.policy_ids):
+                if st[pid]["weights"].size != self.ctx.n_params[p]:
+                    raise ValueError(f"{path}: {pid} holds {st[pid]['weights'].size} parameters, the model "
+                                     f"{self.ctx.n_params[p]}")
+            states[path] = st
+        configured = [float(v) for v in (self.env.target_velocity_list or [0.0])]
+        table = None
+        if any(tvel is not None for _, tvel in members):
+            if len(configured) > 1 and any(tvel is None for _, tvel in members):
+                raise ValueError("evaluate_members: give every member a tvel, or none (the trainer draws from "
+                                 f"{len(configured)} configured velocities)")
+            table = np.repeat([configured[0] if tvel is None else float(tvel) for _, tvel in members], n)
+        ectx = self._eval_context(n_envs)   # holds the trainer's current weights and per-policy filters
+        D = cfg.obs_full_dim
+        if env_filter == "fresh":
+            ectx.filter_set(0.0, np.zeros(D), np.zeros(D))
+        else:
+            ectx.filter_set(*self.rctx.filter_get())
+        current = None   # the trainer's own state, once a checkpoint has overwritten the context's copy
+        henv = N.DevEnv(ectx, seed=seed, target_velocity=configured if len(configured) > 1 else configured[0])
+        try:
+            henv.set_time_limit(num_steps)
+            henv.set_terrain(self.hf_smoothness if hf_smoothness is None else float(hf_smoothness))
+            if table is not None:
+                henv.set_env_target_velocities(table)
+            max_steps = E * num_steps
+            eps = None
+            if explore:
+                gen = torch.Generator(device=self.device)
+                gen.manual_seed(seed + 1)
+                eps = torch.randn((max_steps, n_envs, cfg.n_agents, cfg.act_dim), device=self.device, generator=gen)
+            ectx.eval_begin(E, filter_update=env_filter != "frozen")
+            ectx.eval_members_begin(M)
+            for m, (path, _) in enumerate(members):
+                if path is not None and current is None:
+                    current = [(ectx.params_get(p), ectx.policy_filter_get(p) if cfg.policy_filter else None)
+                               for p in range(cfg.n_policies)]
+                for p, pid in enumerate(self.policy_ids):
+                    if path is not None:
+                        st = states[path][pid]
+                        ectx.params_set(p, st["weights"])
+                        if cfg.policy_filter:
+                            ectx.policy_filter_set(p, *(st["filter"] if st["filter"] is not None else current[p][1]))
+                    elif current is not None:
+                        ectx.params_set(p, current[p][0])
+                        if cfg.policy_filter:
+                            ectx.policy_filter_set(p, *current[p][1])
+                ectx.eval_member_load(m)
+            ectx.eval_devenv(henv, eps, max_steps if explore else 0, max_steps, poll_every=min(25, num_steps))
+            rows = ectx.eval_results().reshape(M, n * E, 6)
+            ectx.eval_end()
+        finally:
+            henv.close()
+        out = []
+        for m in range(M):
+            r = rows[m]
+            r = r[~np.isnan(r[:, 1])][:num_episodes]
+            reward, steps, dist, power, vel, cot = (r[:, i].tolist() for i in range(6))
+            out.append((reward, [int(s) for s in steps], dist, power, vel, cot))
+        return out
+
     def evaluate_sensitivity(self, num_episodes=10, num_steps=1000, rel_step=0.1, steps=None, tvel=None, n_envs=None,
                              env_filter="continue", seed=0, explore=True, env_backend="host", hf_smoothness=None):
         """evaluate() plus the importance matrix of the reference's

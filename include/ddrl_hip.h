@@ -277,6 +277,11 @@ int ddrl_devenv_reset_state(ddrl_devenv* env);
 int ddrl_devenv_set_time_limit(ddrl_devenv* env, int steps);
 int ddrl_devenv_set_target_velocities(ddrl_devenv* env, const float* list, int n);
 int ddrl_devenv_target_velocities(ddrl_devenv* env, float* out, int n_envs);
+/* A fixed target velocity per env: per_env[n_envs] on the host (finite; > 0 with obs_full_dim 44),
+ * or NULL to go back to drawing from the list.  With a table set, env e takes per_env[e] at every
+ * reset and at every episode restart inside the step kernel.  Synchronizes before the table is
+ * replaced; re-keys a captured rollout graph. */
+int ddrl_devenv_set_env_target_velocities(ddrl_devenv* env, const float* per_env, int n_envs);
 int ddrl_devenv_step(ddrl_devenv* env, const float* actions_dev);
 int ddrl_devenv_state_get(ddrl_devenv* env, double* host, size_t n);
 int ddrl_devenv_state_set(ddrl_devenv* env, const double* host, size_t n);
@@ -294,7 +299,7 @@ int ddrl_devenv_terrain_height(ddrl_devenv* env, const int32_t* env_index_dev, c
  * host wait: if reset, ddrl_devenv_reset and observe(env.obs); then for t in [0, T): act(t) ->
  * devenv_step -> reward(t, env.fw, env.cfrc, actions, env.done) -> observe(env.obs); then the
  * bootstrap.  eps_dev[T][N][n_agents][A].  The loop is captured once per (env, eps_dev, env
- * settings: time limit, velocity list, and the terrain settings while the ground is not flat --
+ * settings: time limit, velocity list or per-env velocity table, and the terrain settings while the ground is not flat --
  * a set_terrain or new_terrain between two fragments re-captures) into a HIP graph and replayed (DDRL_ROLLOUT_GRAPH=0 at context creation issues the
  * launches directly); any model kind. */
 int ddrl_rollout_devenv(ddrl_ctx* ctx, ddrl_devenv* env, const float* eps_dev, int reset);
@@ -345,6 +350,31 @@ int ddrl_eval_hostenv(ddrl_ctx* ctx, ddrl_hostenv* env, const float* eps_dev, in
  * synchronization is the progress poll every poll_every steps. */
 int ddrl_eval_devenv(ddrl_ctx* ctx, ddrl_devenv* env, const float* eps_dev, int eps_steps, int max_steps,
                      int poll_every, int* steps_run);
+/* Evaluation members: M parameter sets evaluated side by side on one context, n = n_envs / M envs
+ * each, in one in-order stream of launches -- a whole sweep of the reference's evaluation scripts
+ * (one restored agent per seed / architecture / target velocity cell) as one evaluation.  Member m
+ * owns the envs [m n, (m + 1) n) and holds its own parameters (with the "cup" table), env-side
+ * filter (running stat, delta stat, constants) and per-policy filter state, in device memory
+ * addressed as base + m * stride.  A member computes, bit for bit, what a plain context of n envs
+ * holding the same state computes.
+ *   eval_members_begin: after eval_begin; 1 <= n_members, n_envs % n_members == 0; allocates the
+ *     member storage, all members unloaded.  eval_end (and the next eval_begin) ends the mode;
+ *   eval_member_load: stream-ordered device-to-device copies of the context's CURRENT parameters,
+ *     env-side filter (n, M, S) and per-policy filter state into the member's slot; its delta
+ *     stat starts empty.  Per checkpoint: ddrl_params_set / ddrl_filter_set /
+ *     ddrl_policy_filter_set on the context, then eval_member_load(m);
+ *   eval_member_filter_get: synchronizes; the member's env-side running stat;
+ *   eval_act with the mode on: fails while a member is unloaded ("member k has not been loaded");
+ *     otherwise two launches of the filter push for all members (only when filter_update, or once
+ *     after a load) and one of the forward, grid (row blocks, policies, members).  It reads and
+ *     writes member state only: the context's own parameters and filters are not touched.
+ *     obs / eps / actions / logits_out keep their shapes, envs member-major;
+ *   eval_step / eval_progress / eval_results / eval_devenv: unchanged (they are per env);
+ *   eval_sens_begin and eval_hostenv are refused while the mode is on (sensitivity per member is
+ *     not supported; the host env plane has no per-env target velocity). */
+int ddrl_eval_members_begin(ddrl_ctx* ctx, int n_members);
+int ddrl_eval_member_load(ddrl_ctx* ctx, int member);
+int ddrl_eval_member_filter_get(ddrl_ctx* ctx, int member, double* n, double* M, double* S);
 /* Input sensitivity ("importance matrix") of the evaluated policies
  * (evaluation/rollout_episodes_compute_gradient.py:59-68, :111-122, :167-168): at every step, every
  * non-constant input feature f of every (env, slot) row is moved by -h_f and +h_f, the 2d perturbed
