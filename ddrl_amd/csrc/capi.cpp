@@ -244,6 +244,15 @@ static int validate(const ddrl_cfg& c) {
   if (c.sgd_minibatch_size != 128 && c.sgd_minibatch_size != 256)
     return fail("sgd_minibatch_size must be 128 or 256 (the fused update kernels are built for these two)");
   if (c.num_sgd_iter < 1) return fail("num_sgd_iter must be >= 1");
+  // hyperparameters that can only produce NaN parameters: a NaN itself, and grad_clip <= 0 (the clip
+  // scale is grad_clip * min(1 / norm, 1 / grad_clip)).  lr 0 and grad_clip 1e30 (no clipping) are legal.
+  const struct { const char* name; float v; } hyper[] = {
+      {"gamma", c.gamma}, {"lambda_", c.lambda_}, {"clip_param", c.clip_param}, {"vf_clip_param", c.vf_clip_param},
+      {"vf_loss_coeff", c.vf_loss_coeff}, {"entropy_coeff", c.entropy_coeff}, {"lr", c.lr}, {"grad_clip", c.grad_clip},
+      {"adam_beta1", c.adam_beta1}, {"adam_beta2", c.adam_beta2}, {"adam_eps", c.adam_eps}};
+  for (const auto& h : hyper)
+    if (std::isnan(h.v)) return fail(std::string(h.name) + " is NaN");
+  if (!(c.grad_clip > 0.f)) return fail("grad_clip must be > 0 (pass 1e30 for no clipping)");
   for (int j = 0; j < c.n_agents; ++j)
     if (c.agent_policy[j] < 0 || c.agent_policy[j] >= c.n_policies) return fail("bad agent_policy");
   for (int p = 0; p < c.n_policies; ++p) {

@@ -677,8 +677,15 @@ def explained_variance(y, pred):
 # --------------------------------------------------------------------------------------
 # a15 / a16  clip_by_global_norm and tf1 Adam (training_ops ApplyAdam)
 # --------------------------------------------------------------------------------------
+def grad_clip_value(grad_clip):
+    """RLlib's grad_clip: None means no clipping (clip_by_global_norm below then scales by 1)."""
+    return np.inf if grad_clip is None else grad_clip
+
+
 def clip_by_global_norm(grads, clip_norm=0.5):
     gn = F32(np.sqrt(np.sum([np.sum(np.square(g, dtype=F32)) for g in grads], dtype=F32)))
+    if np.isinf(clip_norm):
+        return [np.asarray(g, F32) for g in grads], gn
     scale = F32(clip_norm) * min(F32(1.0) / gn if gn > 0 else F32(np.inf), F32(1.0) / F32(clip_norm))
     return [(g * scale).astype(F32) for g in grads], gn
 
@@ -758,10 +765,10 @@ def ppo_update(model, params, shapes, adam, batch, shuffle, perms, kl_coeff, cfg
                 batch["logp"][rows], batch["vf_preds"][rows], batch["adv"][rows],
                 batch["vt"][rows], F32(kl_coeff), cfg.get("clip_param", 0.2),
                 cfg.get("vf_clip_param", 10.0), cfg.get("vf_loss_coeff", 0.5),
-                cfg.get("entropy_coeff", 0.0))
+                cfg.get("entropy_coeff", 0.0), cfg.get("vf_clip_mode", "ray10"))
             g = {"ffn": ffn_backward, "cup": cup_backward, "gnn": gnn_backward}[model](p, cache, dlogits, dvalue)
             glist = [g[n] for n, _ in shapes]
-            clipped, gn = clip_by_global_norm(glist, cfg.get("grad_clip", 0.5))
+            clipped, gn = clip_by_global_norm(glist, grad_clip_value(cfg.get("grad_clip", 0.5)))
             flat = np.concatenate([c.reshape(-1) for c in clipped])
             if gradlog is not None:
                 gradlog.append(flat.copy())

@@ -232,11 +232,11 @@ def run_rollout(ctx, cfg, inst, params, rng, filt, T, orc_cls=None, pfilt=None):
     return orc, norms, np.stack(acts_gpu), np.stack(acts_orc)
 
 
-def oracle_rollout(cfg, inst, params, rng, filt, T):
+def oracle_rollout(cfg, inst, params, rng, filt, T, orc_cls=None):
     """The oracle's half of run_rollout alone (no device): the same inputs from the same rng, the
     oracle consuming its own actions.  Returns (oracle, eps)."""
     obs, eps, fw, cfrc, done = synthetic_inputs(rng, cfg, T)
-    orc = OracleRollout(cfg, inst, params, filt)
+    orc = (orc_cls or OracleRollout)(cfg, inst, params, filt)
     for t in range(T):
         orc.observe(obs[t])
         orc.reward(t, fw[t], cfrc[t], orc.act(t, eps[t]), done[t])
@@ -253,7 +253,8 @@ CUP_ENV = "QuantrupedMultiEnv_SharedDecentralLegID"
 CUP_CONFIG = {"model": {"custom_model": "cup"}}
 
 
-def init_cup_params(ctx, cfg, seed, head_scale=30.0, perturb=True):
+def make_cup_params(cfg, seed, head_scale=30.0, perturb=True):
+    """The seeded "cup" parameters (a one-policy list of oracle dicts)."""
     rng = np.random.default_rng(seed)
     A, d = cfg.act_dim, cfg.obs_dim[0]
     pr = O.cup_init(rng, d, A)
@@ -263,8 +264,13 @@ def init_cup_params(ctx, cfg, seed, head_scale=30.0, perturb=True):
     pr["fc_out/bias"] += np.concatenate([np.zeros(A), -0.5 * np.ones(A)]).astype(np.float32)
     if perturb:   # off the +-1 start so that every coupling entry scales differently
         pr["leg_coupling"] = (pr["leg_coupling"] * rng.uniform(0.5, 1.5, size=(4, A))).astype(np.float32)
-    ctx.params_set(0, O.pack(pr, O.cup_param_shapes(d, A)))
     return [pr]
+
+
+def init_cup_params(ctx, cfg, seed, head_scale=30.0, perturb=True):
+    params = make_cup_params(cfg, seed, head_scale, perturb)
+    ctx.params_set(0, O.pack(params[0], O.cup_param_shapes(cfg.obs_dim[0], cfg.act_dim)))
+    return params
 
 
 def init_policy_params(ctx, cfg, seed, cup):
@@ -288,13 +294,19 @@ class CupOracleRollout(OracleRollout):
 GNN_ENV = "QuantrupedMultiEnv_DecentralShared_Graph"
 
 
-def init_gnn_params(ctx, seed, head_scale=1.0, A=2, layer="mpnn"):
+def make_gnn_params(seed, head_scale=1.0, A=2, layer="mpnn"):
+    """The seeded GraphNet parameters (one oracle dict)."""
     rng = np.random.default_rng(seed)
     p = O.gnn_init(rng, 2 * A, layer=layer)
     for net in ("actor/", "critic/"):
         p[net + "linear_out/kernel"] *= head_scale
         p[net + "state_enc/bias"] += (rng.normal(size=p[net + "state_enc/bias"].shape) * 0.2).astype(np.float32)
     p["actor/linear_out/bias"] += np.concatenate([np.zeros(A), -0.5 * np.ones(A)]).astype(np.float32)
+    return p
+
+
+def init_gnn_params(ctx, seed, head_scale=1.0, A=2, layer="mpnn"):
+    p = make_gnn_params(seed, head_scale, A, layer)
     ctx.params_set(0, O.pack(p, O.gnn_param_shapes(2 * A, layer=layer)))
     return p
 
@@ -340,6 +352,132 @@ class GnnOracleRollout(OracleRollout):
 
     def bootstrap(self):
         self.last_v = [self._forward_all()[3]]
+
+
+# --------------------------------------------------------------------------------------
+# Update tests away from the default hyperparameters (tests/test_gpu_update_hyper.py, and the
+# oracle's own autograd check in tests/test_oracle.py).  RLlib-style config keys: make_cfg and
+# the oracle's cfg dict read the same ones; "kl_coeff" is what the test passes to the update.
+# --------------------------------------------------------------------------------------
+HYPER_SETS = {
+    "H1": {"entropy_coeff": 0.01},
+    "H2": {"entropy_coeff": 0.01, "clip_param": 0.1, "vf_clip_param": 0.5, "vf_loss_coeff": 1.0},
+    "H3": {"vf_clip_mode": "squared", "vf_clip_param": 1.0, "clip_param": 0.3, "entropy_coeff": -0.005},
+    "H4": {"grad_clip": None, "lr": 1e-3},
+    "H5": {"grad_clip": 40.0, "kl_coeff": 0.0},
+    "H6": {"grad_clip": 0.05, "lr": 1e-4},
+}
+BRANCH_FLOOR = 0.05   # least share of a minibatch's rows on each side of each clip decision
+
+
+def branch_shares(logits, value, b, cfg):
+    """The share of rows on the gradient-passing side of each clip decision that the cfg's value
+    clip mode uses, in fp64: {"surrogate passes", and "value inside clip" + "vf1 >= vf2" (ray10) or
+    "sq <= vf_clip" (squared)}.  b: the rows' batch columns (actions, logp, vf_preds, adv, vt)."""
+    clip, vf_clip = cfg.get("clip_param", 0.2), cfg.get("vf_clip_param", 10.0)
+    pol_on, _, _, m_sq, m_in = O.ppo_branches(logits, value, b["actions"], b["logp"], b["vf_preds"], b["adv"],
+                                              b["vt"], clip_param=clip, vf_clip_param=vf_clip)
+    out = {"surrogate passes": float(np.mean(pol_on))}
+    if cfg.get("vf_clip_mode", "ray10") == "ray10":
+        out["value inside clip"] = float(np.mean(m_in >= 0))
+        out["vf1 >= vf2"] = float(np.mean(m_sq >= 0))
+    else:
+        sq = (np.asarray(value, np.float64) - np.asarray(b["vt"], np.float64)) ** 2
+        out["sq <= vf_clip"] = float(np.mean(sq <= vf_clip))
+    return out
+
+
+def assert_branch_floor(shares, msg=""):
+    """Both sides of every decision hold at least BRANCH_FLOOR of the rows."""
+    for name, share in shares.items():
+        assert BRANCH_FLOOR <= share <= 1 - BRANCH_FLOOR, (msg, name, share, shares)
+
+
+_MODEL_ROLLOUT = {"ffn": None, "cup": CupOracleRollout, "gnn": GnnOracleRollout}
+
+
+def make_model_params(cfg, model, seed):
+    """Unit-head seeded parameters of every policy, host only: a list of oracle dicts."""
+    if model == "cup":
+        return make_cup_params(cfg, seed, head_scale=1.0)
+    if model == "gnn":
+        return [make_gnn_params(seed, head_scale=1.0)]
+    return make_params(cfg, seed, head_scale=1.0)
+
+
+def model_shapes(cfg, model, p):
+    d, A = cfg.obs_dim[p], cfg.act_dim
+    return {"ffn": lambda: O.ffn_param_shapes(d, 2 * A), "cup": lambda: O.cup_param_shapes(d, A),
+            "gnn": lambda: O.gnn_param_shapes(2 * A)}[model]()
+
+
+class StraddlingBatch:
+    """An update batch built on the host (no device rollout) whose rows sit on both sides of every
+    clip decision at the starting parameters.
+
+    The oracle rolls out the seeded synthetic inputs (oracle_rollout / its cup and gnn
+    counterparts), runs GAE, and then one seeded generator perturbs the behaviour columns:
+    logp_old += N(0, clip_param) and, under the ray10 value clip only, vf_preds += N(0, vf_clip_param).
+    (Fed unperturbed, the records come from the parameters the update starts at: ratio = 1 and
+    V - vf_old = 0 at step 0, so no clip decision is near its threshold for many steps.)  The
+    perturbed columns are part of records(p, lay), the array for records_set, and of batches[p],
+    what the oracle reads: the same rows on both sides.
+
+    shares[p]: branch_shares of the first minibatch of policy p's schedule, from the fp64 oracle's
+    forward at the starting parameters; the schedule is sgd_schedule(default_rng(100 + p))."""
+
+    def __init__(self, cfg, inst, params, model="ffn", hyper=None, seed=11, rollout_seed=5, mb=128):
+        import copy
+        hyper = hyper or {}
+        T = cfg.frag_len
+        rng = np.random.default_rng(rollout_seed)
+        filt = filter_state(cfg.obs_full_dim, rng)
+        prm = params[0] if model == "gnn" else params
+        orc, _ = oracle_rollout(cfg, inst, prm, rng, filt, T, orc_cls=_MODEL_ROLLOUT[model])
+        self.norms = orc.gae()
+        prng = np.random.default_rng(seed)
+        self.orc = copy.copy(orc)
+        self.orc.rec = []
+        for r in orc.rec:
+            r = dict(r)
+            r["logp"] = (r["logp"] + prng.normal(size=r["logp"].shape) * hyper.get("clip_param", 0.2)).astype(np.float32)
+            if hyper.get("vf_clip_mode", "ray10") == "ray10":
+                r["vf"] = (r["vf"] + prng.normal(size=r["vf"].shape) * hyper.get("vf_clip_param", 10.0)).astype(np.float32)
+            self.orc.rec.append(r)
+        O64 = O.with_dtype(np.float64)
+        self.batches, self.shuffles, self.perms, self.shares = [], [], [], []
+        for p in range(cfg.n_policies):
+            r = self.orc.rec[p]
+            R = r["logp"].size
+            mean, den = self.norms[p]
+            b = dict(actions=r["act"].reshape(R, -1), logits=r["logits"].reshape(R, -1), logp=r["logp"].reshape(-1),
+                     vf_preds=r["vf"].reshape(-1), adv=((r["adv"].reshape(-1) - mean) / den).astype(np.float32),
+                     vt=r["vt"].reshape(-1))
+            obs = r["obs"].reshape(R, -1)
+            if model == "gnn":
+                b["X"], b["node_idx"] = obs[:, :92].reshape(-1, 4, 23), obs[:, 92].astype(np.int64)
+            else:
+                b["obs"] = obs
+            if model == "cup":
+                k = len(orc.slots[p])
+                b["leg"] = np.tile(np.arange(R // T) % k, T).astype(np.int64)
+            sh, pe = O.sgd_schedule(np.random.default_rng(100 + p), R, mb, cfg.num_sgd_iter)
+            rows = O.minibatch_rows(sh, pe, 0, 0, mb)
+            p64 = {k_: np.asarray(v, np.float64) for k_, v in params[p].items()}
+            if model == "gnn":
+                logits, value, _ = O64.gnn_forward(p64, b["X"][rows], b["node_idx"][rows])
+            elif model == "cup":
+                logits, value, _ = O64.cup_forward(p64, b["obs"][rows], b["leg"][rows])
+            else:
+                logits, value, _ = O64.ffn_forward(p64, b["obs"][rows])
+            self.shares.append(branch_shares(logits, value, {k_: v[rows] for k_, v in b.items()}, hyper))
+            self.batches.append(b)
+            self.shuffles.append(sh)
+            self.perms.append(pe)
+
+    def records(self, p, lay):
+        """Policy p's record array in the context's layout, perturbed columns included."""
+        return self.orc.flat_records(p, lay)
 
 
 def drift_check(got, model, params, shapes, batch, sh, pe, kl, steps, factor=4.0, floor=2e-7, cfg=None):

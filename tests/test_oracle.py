@@ -8,6 +8,7 @@ import torch
 
 from oracle import ddrl_oracle as O
 from ddrl_amd.simulation_envs import layouts as L
+from tests.gpu_harness import HYPER_SETS, assert_branch_floor, branch_shares
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -105,14 +106,18 @@ def _torch_ppo_loss(logits, v, batch, beta, cfg):
             - ls.sum(1))
     ratio = torch.exp(logp - T("logp"))
     adv = T("adv")
-    surr = torch.minimum(adv * ratio, adv * torch.clamp(ratio, 0.8, 1.2))
+    clip, vf_clip = cfg.get("clip_param", 0.2), cfg.get("vf_clip_param", 10.0)
+    surr = torch.minimum(adv * ratio, adv * torch.clamp(ratio, 1 - clip, 1 + clip))
     om, os_ = ol[:, :A], ol[:, A:]
     kl = (ls - os_ + (os_.exp() ** 2 + (om - mean) ** 2) / (2 * ls.exp() ** 2) - 0.5).sum(1)
     vf1 = (v - T("vt")) ** 2
-    vf2 = (T("vf_preds") + torch.clamp(v - T("vf_preds"), -10, 10) - T("vt")) ** 2
-    vf = torch.maximum(vf1, vf2)
+    if cfg.get("vf_clip_mode", "ray10") == "ray10":
+        vf2 = (T("vf_preds") + torch.clamp(v - T("vf_preds"), -vf_clip, vf_clip) - T("vt")) ** 2
+        vf = torch.maximum(vf1, vf2)
+    else:   # "squared": later RLlib's clip of the square
+        vf = torch.clamp(vf1, 0, vf_clip)
     ent = (ls + 0.5 * np.log(2 * np.pi * np.e)).sum(1)
-    return (-surr + beta * kl + 0.5 * vf - cfg.get("entropy_coeff", 0.0) * ent).mean()
+    return (-surr + beta * kl + cfg.get("vf_loss_coeff", 0.5) * vf - cfg.get("entropy_coeff", 0.0) * ent).mean()
 
 
 def _rand_batch(rng, n, d, A=2, X=None):
@@ -128,8 +133,28 @@ def _rand_batch(rng, n, d, A=2, X=None):
     return b
 
 
-@pytest.mark.parametrize("d", [19, 35, 43])
-def test_ffn_ppo_gradients_match_autograd(d):
+def _loss_kwargs(cfg):
+    """ppo_loss_rows' hyperparameter arguments from an RLlib-style cfg (its defaults otherwise)."""
+    return {k: cfg[k] for k in ("clip_param", "vf_clip_param", "vf_loss_coeff", "entropy_coeff", "vf_clip_mode")
+            if k in cfg}
+
+
+def _straddle(b, cfg, seed=11):
+    """Perturb the batch's old logp by N(0, clip_param) and, under the ray10 value clip, its old
+    value predictions by N(0, vf_clip_param): rows on both sides of every clip decision."""
+    rng = np.random.default_rng(seed)
+    n = b["logp"].shape[0]
+    b["logp"] = (b["logp"] + rng.normal(size=n) * cfg.get("clip_param", 0.2)).astype(np.float32)
+    if cfg.get("vf_clip_mode", "ray10") == "ray10":
+        b["vf_preds"] = (b["vf_preds"] + rng.normal(size=n) * cfg.get("vf_clip_param", 10.0)).astype(np.float32)
+
+
+def _assert_both_sides(logits, value, b, cfg):
+    """Every side of every clip decision the cfg's mode uses holds its floor of the rows."""
+    assert_branch_floor(branch_shares(logits, value, b, cfg))
+
+
+def _check_ffn(d, cfg, beta, straddle):
     rng = np.random.default_rng(d)
     A = 8 if d == 43 else 2
     p = O.ffn_init(rng, d, 2 * A)
@@ -137,10 +162,13 @@ def test_ffn_ppo_gradients_match_autograd(d):
     p["fc_out/kernel"] *= 30
     p["value_out/kernel"] *= 30
     b = _rand_batch(rng, 128, d, A)
-    beta, cfg = 0.3, {}
+    if straddle:
+        _straddle(b, cfg)
     logits, value, cache = O.ffn_forward(p, b["obs"])
+    if straddle:
+        _assert_both_sides(logits, value, b, cfg)
     dl, dv, st = O.ppo_loss_rows(logits, value, b["actions"], b["logits"], b["logp"],
-                                 b["vf_preds"], b["adv"], b["vt"], np.float32(beta))
+                                 b["vf_preds"], b["adv"], b["vt"], np.float32(beta), **_loss_kwargs(cfg))
     g = O.ffn_backward(p, cache, dl, dv)
     t, loss = _torch_ffn_loss(p, b, beta, cfg)
     loss.backward()
@@ -150,9 +178,18 @@ def test_ffn_ppo_gradients_match_autograd(d):
         np.testing.assert_allclose(g[k], ref, rtol=1e-4, atol=2e-5 * np.abs(ref).max(), err_msg=k)
 
 
+@pytest.mark.parametrize("d", [19, 35, 43])
+def test_ffn_ppo_gradients_match_autograd(d):
+    _check_ffn(d, {}, 0.3, False)
+
+
 def test_cup_gradients_match_autograd():
     """"cup" (models/coupling_net_glorot_uniform_init.py:22-30): coupled means, including
     the gradient of the trainable leg-coupling table, against torch autograd."""
+    _check_cup({}, 0.3, False)
+
+
+def _check_cup(cfg, beta, straddle):
     rng = np.random.default_rng(7)
     d, A, n = 19, 2, 128
     p = O.cup_init(rng, d, A)
@@ -162,10 +199,13 @@ def test_cup_gradients_match_autograd():
     p["value_out/kernel"] *= 30
     b = _rand_batch(rng, n, d, A)
     leg = rng.integers(0, 4, size=n)
-    beta = 0.3
+    if straddle:
+        _straddle(b, cfg)
     logits, value, cache = O.cup_forward(p, b["obs"], leg)
+    if straddle:
+        _assert_both_sides(logits, value, b, cfg)
     dl, dv, st = O.ppo_loss_rows(logits, value, b["actions"], b["logits"], b["logp"],
-                                 b["vf_preds"], b["adv"], b["vt"], np.float32(beta))
+                                 b["vf_preds"], b["adv"], b["vt"], np.float32(beta), **_loss_kwargs(cfg))
     g = O.cup_backward(p, cache, dl, dv)
     t = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in p.items()}
     x = torch.tensor(b["obs"], dtype=torch.float64)
@@ -175,7 +215,7 @@ def test_cup_gradients_match_autograd():
     g2 = torch.tanh(torch.tanh(x @ t["fc_value_1/kernel"] + t["fc_value_1/bias"]) @ t["fc_value_2/kernel"]
                     + t["fc_value_2/bias"])
     v = (g2 @ t["value_out/kernel"] + t["value_out/bias"])[:, 0]
-    loss = _torch_ppo_loss(raw * coef, v, b, beta, {})
+    loss = _torch_ppo_loss(raw * coef, v, b, beta, cfg)
     loss.backward()
     assert abs(loss.item() - st["total_loss"]) < 1e-5 * max(1, abs(loss.item()))
     assert np.abs(g["leg_coupling"]).max() > 0
@@ -185,17 +225,24 @@ def test_cup_gradients_match_autograd():
 
 
 def test_gnn_gradients_match_autograd():
+    _check_gnn({}, 0.2, False, 32)
+
+
+def _check_gnn(cfg, beta, straddle, n):
     rng = np.random.default_rng(5)
     p = O.gnn_init(rng, 4)
     p["actor/linear_out/kernel"] *= 30
     p["critic/linear_out/kernel"] *= 30
-    n = 32
     X = rng.normal(size=(n, 4, 23)).astype(np.float32)
     node = rng.integers(0, 4, size=n)
     b = _rand_batch(rng, n, 0, 2, X=True)
+    if straddle:
+        _straddle(b, cfg)
     logits, value, cache = O.gnn_forward(p, X, node)
+    if straddle:
+        _assert_both_sides(logits, value, b, cfg)
     dl, dv, st = O.ppo_loss_rows(logits, value, b["actions"], b["logits"], b["logp"],
-                                 b["vf_preds"], b["adv"], b["vt"], np.float32(0.2))
+                                 b["vf_preds"], b["adv"], b["vt"], np.float32(beta), **_loss_kwargs(cfg))
     g = O.gnn_backward(p, cache, dl, dv)
 
     t = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in p.items()}
@@ -213,12 +260,33 @@ def test_gnn_gradients_match_autograd():
         ys = y[torch.arange(n), torch.tensor(node)]
         return ys @ t[pre + "linear_out/kernel"] + t[pre + "linear_out/bias"]
 
-    loss = _torch_ppo_loss(net("actor/"), net("critic/")[:, 0], b, 0.2, {})
+    loss = _torch_ppo_loss(net("actor/"), net("critic/")[:, 0], b, beta, cfg)
     loss.backward()
     assert abs(loss.item() - st["total_loss"]) < 1e-5 * max(1, abs(loss.item()))
     for k in p:
         ref = t[k].grad.numpy()
         np.testing.assert_allclose(g[k], ref, rtol=1e-4, atol=2e-5 * np.abs(ref).max(), err_msg=k)
+
+
+@pytest.mark.parametrize("d", [19, 43])
+@pytest.mark.parametrize("hyper", sorted(HYPER_SETS))
+def test_ffn_ppo_gradients_match_autograd_under_hyperparameters(hyper, d):
+    """The oracle's analytic gradient against torch fp64 away from the default hyperparameters
+    (tests/gpu_harness.HYPER_SETS: entropy term, other clip widths and value coefficient, the
+    squared value clip, kl_coeff 0), on rows that sit on both sides of every clip decision."""
+    cfg = HYPER_SETS[hyper]
+    _check_ffn(d, cfg, cfg.get("kl_coeff", 0.3), True)
+
+
+@pytest.mark.parametrize("hyper", ["H2", "H3"])
+def test_cup_gradients_match_autograd_under_hyperparameters(hyper):
+    _check_cup(HYPER_SETS[hyper], 0.3, True)
+
+
+@pytest.mark.parametrize("hyper", ["H2", "H3"])
+def test_gnn_gradients_match_autograd_under_hyperparameters(hyper):
+    # 128 rows: with 32, one side of a decision can hold a single row
+    _check_gnn(HYPER_SETS[hyper], 0.2, True, 128)
 
 
 def _torch_gnn_layer(layer, t, pre, x, adj):
