@@ -36,7 +36,9 @@ _VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 #    A = 2 and A = 4 instances spill nothing either way, the A = 8 ones 256 / 288 bytes of scratch
 #    per lane against 1808 / 1968 with it and 400 / 448 with neither flag (DESIGN.md section 3,
 #    "256-row minibatches")
+#  * the group update (ppo_ffn_group.hip) is ppo_ffn.hip's kernel with a chain axis: the same flags
 SRC_FLAGS = {"ppo_ffn.hip": _ILP + _VGPR_MFMA, "ppo_ffn_peer.hip": _ILP + _VGPR_MFMA, "gnn.hip": _VGPR_MFMA,
+             "ppo_ffn_group.hip": _ILP + _VGPR_MFMA,
              "ppo_ffn_atomic.hip": _VGPR_MFMA, "ppo_ffn_mb256.hip": _VGPR_MFMA,
              "ppo_ffn_mb256_atomic.hip": _VGPR_MFMA,
              # the device env plane matches the host plane's arithmetic: no a * b + c -> fma

@@ -2301,3 +2301,290 @@ int ddrl_device_buffers(ddrl_ctx* c, int pid, void** records, void** last_v, voi
 }
 
 }  // extern "C"
+
+// ---- group update (ppo_ffn_group.hip): the fused updates of M same-shaped contexts in one launch ----
+// Chain g = m * P + p is policy p of member m.  The launches of a run hold whole members, in member
+// order; launch l covers the chains [g0_l, g0_l + n_l) of the table and records its blocks' XCC ids
+// at xcc + (sum of the earlier launches' grids).  The arenas (norm granules, outboxes) are sized for
+// one launch's chains and shared by the launches of a run, which are ordered by the stream.
+struct ddrl_update_group {
+  std::vector<ddrl_ctx*> members;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int P = 0, cap = 0;                  // policies per member, chains per launch
+  std::vector<int32_t> launch_of_member, first_block;
+  std::vector<int> launch_g0, launch_n, launch_x0;   // first chain, chains and first xcc slot of each launch
+  int xcc_total = 0;
+  UpdateArgs* table_host = nullptr;    // pinned; rewritten only after `copied` (recorded behind its H2D copy)
+  UpdateArgs* table_dev = nullptr;
+  hipEvent_t copied = nullptr;
+  int copy_pending = 0;
+  unsigned long long *xchg = nullptr, *gx = nullptr;
+  int *err = nullptr, *xcc = nullptr;
+  std::vector<int> xcc_host;           // the record of the last finished run
+  unsigned epoch = 0;                  // launches so far (granule tag epochs), the group's own
+  int inflight = 0;                    // a run is enqueued and not yet finished
+  int refused = 0;                     // a placement check failed: no further runs
+};
+
+namespace {
+int group_plan(int M, int P, int max_chains, int32_t* launch_of_member, int32_t* first_block) {
+  if (M < 1) return fail("update group: at least one member is needed");
+  if (P < 1 || P > DDRL_MAXP) return fail("update group: n_policies must be 1 .. " + std::to_string(DDRL_MAXP));
+  if (max_chains < P)
+    return fail("update group: a launch of at most " + std::to_string(max_chains) + " chains cannot hold a member's " +
+                std::to_string(P) + " (members are never split across launches)");
+  const int per = max_chains / P;   // whole members per launch
+  for (int m = 0; m < M; ++m) {
+    if (launch_of_member) launch_of_member[m] = m / per;
+    for (int p = 0; p < P && first_block; ++p) {
+      const int lc = (m % per) * P + p;   // chain index inside its launch
+      first_block[m * P + p] = 32 * (lc >> 3) + (lc & 7);
+    }
+  }
+  return 0;
+}
+
+std::string member_name(int m) { return "update group: member " + std::to_string(m); }
+
+// what a member must still be at every run (create checks it too): the group's stream, the default
+// exchange protocol, no peer
+int group_member_ok(const ddrl_update_group* g, int m) {
+  const ddrl_ctx* c = g->members[m];
+  if (c->stream != g->stream) return fail(member_name(m) + " is on another stream than member 0");
+  if (c->xchg_atomic)
+    return fail(member_name(m) + " is on the atomic exchange protocol (DDRL_XCHG=atomic, or switched after a failed "
+                "placement check); the group kernel has the default protocol only");
+  if (c->peer_gx || c->peer_rank >= 0) return fail(member_name(m) + " is attached to a peer (ddrl_peer_attach)");
+  return 0;
+}
+
+// the first difference between member m's configuration and member 0's in anything the update reads
+int group_same_shape(const ddrl_ctx* a, const ddrl_ctx* b, int m) {
+  const ddrl_cfg &x = a->cfg, &y = b->cfg;
+  const char* why = nullptr;
+#define DDRL_GRP_SAME(f) if (!why && !(x.f == y.f)) why = #f
+  DDRL_GRP_SAME(model_kind); DDRL_GRP_SAME(n_policies); DDRL_GRP_SAME(act_dim); DDRL_GRP_SAME(leg_coupling);
+  DDRL_GRP_SAME(sgd_minibatch_size); DDRL_GRP_SAME(num_sgd_iter); DDRL_GRP_SAME(clip_param);
+  DDRL_GRP_SAME(vf_clip_param); DDRL_GRP_SAME(vf_loss_coeff); DDRL_GRP_SAME(entropy_coeff); DDRL_GRP_SAME(lr);
+  DDRL_GRP_SAME(grad_clip); DDRL_GRP_SAME(adam_beta1); DDRL_GRP_SAME(adam_beta2); DDRL_GRP_SAME(adam_eps);
+  DDRL_GRP_SAME(vf_clip_mode);
+#undef DDRL_GRP_SAME
+  for (int p = 0; p < x.n_policies && !why; ++p) {
+    const Policy &P = a->pol[p], &Q = b->pol[p];
+    if (P.d != Q.d) why = "obs_dim";
+    else if (std::memcmp(&P.lay, &Q.lay, sizeof(RecLayout)) != 0) why = "the record layout";
+    else if (P.R != Q.R || P.nb != Q.nb) why = "frag_len x n_envs (rows per policy)";
+    else if (P.n_params != Q.n_params) why = "the parameter count";
+  }
+  if (why) return fail(member_name(m) + " differs from member 0 in " + why + ": a group takes contexts of one shape");
+  return 0;
+}
+
+void group_free(ddrl_update_group* g) {
+  if (g->copied) (void)hipEventDestroy(g->copied);
+  if (g->table_host) (void)hipHostFree(g->table_host);
+  for (void* p : {(void*)g->table_dev, (void*)g->xchg, (void*)g->gx, (void*)g->err, (void*)g->xcc})
+    if (p) (void)hipFree(p);
+  delete g;
+}
+}  // namespace
+
+extern "C" {
+
+int ddrl_update_group_plan(int n_members, int n_policies, int max_chains, int32_t* launch_of_member,
+                           int32_t* first_block_of_chain) {
+  return group_plan(n_members, n_policies, max_chains, launch_of_member, first_block_of_chain);
+}
+
+int ddrl_update_group_create(ddrl_ctx* const* members, int n_members, int max_chains_per_launch,
+                             ddrl_update_group** out) {
+  if (!members || !out) return fail("null argument");
+  if (n_members < 1) return fail("update group: at least one member is needed");
+  if (max_chains_per_launch < 0) return fail("update group: max_chains_per_launch must be >= 0 (0: the device's cap)");
+  for (int m = 0; m < n_members; ++m) {
+    if (!members[m]) return fail(member_name(m) + " is a null context");
+    for (int k = 0; k < m; ++k)
+      if (members[k] == members[m]) return fail(member_name(m) + " repeats member " + std::to_string(k));
+  }
+  ddrl_ctx* c0 = members[0];
+  HIPCHK(hipSetDevice(c0->device));
+  ddrl_update_group* g = new ddrl_update_group();
+  g->members.assign(members, members + n_members);
+  g->device = c0->device;
+  g->stream = c0->stream;
+  g->P = c0->cfg.n_policies;
+  int rc = 0;
+  for (int m = 0; m < n_members && !rc; ++m) {
+    const ddrl_ctx* c = members[m];
+    if (c->device != g->device) rc = fail(member_name(m) + " is on another device than member 0");
+    else if (c->cfg.model_kind != DDRL_MODEL_FFN) rc = fail(member_name(m) + " is a GraphNet context: the group update runs the fcnet kernels only");
+    else if (c->cfg.sgd_minibatch_size != 128) rc = fail(member_name(m) + " has sgd_minibatch_size " + std::to_string(c->cfg.sgd_minibatch_size) + ": the group kernel is built for 128-row minibatches only");
+    else if (c->update_split != 2) rc = fail(member_name(m) + " was created under DDRL_UPDATE_SPLIT=1: the group kernel is the row split");
+    else rc = group_member_ok(g, m) || group_same_shape(c, c0, m);
+  }
+  int cus = 0;
+  if (!rc && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess)
+    rc = fail("update group: cannot read the device's CU count");
+  if (!rc) {
+    // one workgroup per CU (by LDS), four per chain, a chain's four on one XCD: with the CUs in 8
+    // XCDs, floor((CUs / 8) / 4) chains per XCD are resident together
+    g->cap = 8 * ((cus / 8) / 4);
+    if (max_chains_per_launch > 0) g->cap = std::min(g->cap, max_chains_per_launch);
+    g->launch_of_member.resize(n_members);
+    g->first_block.resize((size_t)n_members * g->P);
+    rc = group_plan(n_members, g->P, g->cap, g->launch_of_member.data(), g->first_block.data());
+  }
+  if (!rc) {
+    const int nl = g->launch_of_member.back() + 1;
+    g->launch_g0.assign(nl, 0); g->launch_n.assign(nl, 0); g->launch_x0.assign(nl, 0);
+    for (int m = 0; m < n_members; ++m) g->launch_n[g->launch_of_member[m]] += g->P;
+    int maxn = 0;
+    for (int l = 0; l < nl; ++l) {
+      g->launch_g0[l] = l ? g->launch_g0[l - 1] + g->launch_n[l - 1] : 0;
+      g->launch_x0[l] = g->xcc_total;
+      g->xcc_total += update_group_grid(g->launch_n[l]);
+      maxn = std::max(maxn, g->launch_n[l]);
+    }
+    const size_t nchain = (size_t)n_members * g->P, rows8 = 8 * (size_t)((maxn + 7) / 8);
+    auto dev = [&](void** p, size_t bytes) {
+      return hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess;
+    };
+    if (hipHostMalloc((void**)&g->table_host, nchain * sizeof(UpdateArgs), hipHostMallocDefault) != hipSuccess ||
+        !dev((void**)&g->table_dev, nchain * sizeof(UpdateArgs)) ||
+        !dev((void**)&g->xchg, sizeof(unsigned long long) * 8 * rows8) || !dev((void**)&g->gx, gx_bytes(maxn)) ||
+        !dev((void**)&g->err, sizeof(int)) || !dev((void**)&g->xcc, sizeof(int) * (size_t)g->xcc_total) ||
+        hipEventCreateWithFlags(&g->copied, hipEventDisableTiming) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      rc = fail("update group: allocation failed (" + std::to_string(gx_bytes(maxn) >> 20) + " MB of outboxes)");
+    g->xcc_host.assign(g->xcc_total, -1);
+  }
+  if (rc) {
+    group_free(g);
+    return -1;
+  }
+  *out = g;
+  return 0;
+}
+
+int ddrl_update_group_run(ddrl_update_group* g, const int32_t* const* shuffle, const int32_t* const* perm,
+                          const float* kl, int max_steps) {
+  if (!g) return fail("null update group");
+  if (!shuffle || !perm || !kl) return fail("null update argument");
+  if (g->refused)
+    return fail("update group: an earlier run failed the placement check (a chain's workgroups ran on different "
+                "XCDs), and the group kernel has no protocol for that: update the members one by one "
+                "(ddrl_ppo_update, which switches to the atomic exchange)");
+  if (g->inflight) return fail("update group: the previous run has not been finished (ddrl_update_group_finish)");
+  const int M = (int)g->members.size(), P = g->P;
+  ddrl_ctx* c0 = g->members[0];
+  for (int m = 0; m < M; ++m) {
+    if (group_member_ok(g, m)) return -1;
+    for (int p = 0; p < P; ++p) {
+      if (!shuffle[m * P + p] || !perm[m * P + p])
+        return fail(member_name(m) + ": null shuffle/perm for policy " + std::to_string(p));
+      if (g->members[m]->pol[p].R < 128)
+        return fail(member_name(m) + ", policy " + std::to_string(p) + ": the train batch holds " +
+                    std::to_string(g->members[m]->pol[p].R) + " rows, fewer than one minibatch");
+    }
+  }
+  HIPCHK(hipSetDevice(g->device));
+  // the pinned table is the source of the previous run's H2D copy: wait for that copy before rewriting it
+  if (g->copy_pending) {
+    HIPCHK(hipEventSynchronize(g->copied));
+    g->copy_pending = 0;
+  }
+  int maxd = 0, maxs = 0, hook = 0;
+  for (int m = 0; m < M; ++m) {
+    ddrl_ctx* c = g->members[m];
+    hook |= c->fail_step >= 0;
+    for (int p = 0; p < P; ++p) {
+      UpdateArgs& u = g->table_host[m * P + p];
+      u = make_update(c, p, shuffle[m * P + p], perm[m * P + p], kl[m * P + p]);
+      u.max_steps = max_steps;
+      c->kl_last[p] = kl[m * P + p];
+      const int total = c->cfg.num_sgd_iter * c->pol[p].nb;
+      c->pol[p].last_steps = max_steps >= 0 ? std::min(total, max_steps) : total;
+      maxd = std::max(maxd, u.d), maxs = std::max(maxs, u.lay.stride);
+    }
+    if (snapshot(c, (1 << P) - 1)) return -1;
+  }
+  HIPCHK(hipMemcpyAsync(g->table_dev, g->table_host, sizeof(UpdateArgs) * (size_t)M * P, hipMemcpyHostToDevice, g->stream));
+  HIPCHK(hipEventRecord(g->copied, g->stream));
+  g->copy_pending = 1;
+  // test hook (DDRL_TEST_FAIL_STEP on any member): the run starts with the group's error word set,
+  // as launch_ffn does for a context -- every chain runs its steps and none writes back
+  if (hook) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)g->err, 1, 1, g->stream));
+  const UpdateHyper h = make_hyper(c0, P);
+  for (size_t l = 0; l < g->launch_n.size(); ++l)
+    if (launch_update_ffn_group(g->stream, g->table_dev + g->launch_g0[l], g->launch_n[l], h, c0->cfg.act_dim, maxd, maxs,
+                                c0->cfg.leg_coupling, g->xchg, g->gx, g->err, &g->epoch, g->xcc + g->launch_x0[l])) {
+      for (ddrl_ctx* c : g->members) c->snap_mask = 0;   // nothing ran: nothing to restore
+      (void)hipMemsetAsync(g->err, 0, sizeof(int), g->stream);
+      return fail("update group: this library was built without the group kernel (a diagnostic build); nothing ran");
+    }
+  g->inflight = 1;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ddrl_update_group_finish(ddrl_update_group* g) {
+  if (!g) return fail("null update group");
+  if (!g->inflight) return 0;
+  HIPCHK(hipSetDevice(g->device));
+  HIPCHK(hipStreamSynchronize(g->stream));
+  g->inflight = 0;
+  g->copy_pending = 0;
+  HIPCHK(hipGetLastError());
+  int e = 0;
+  HIPCHK(hipMemcpy(&e, g->err, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(g->xcc_host.data(), g->xcc, sizeof(int) * g->xcc_host.size(), hipMemcpyDeviceToHost));
+  int bad = 0;
+  for (size_t l = 0; l < g->launch_n.size(); ++l)
+    for (int lc = 0; lc < g->launch_n[l]; ++lc) {
+      const int* x = g->xcc_host.data() + g->launch_x0[l] + 32 * (lc >> 3) + (lc & 7);
+      for (int j = 1; j < 4; ++j) bad |= x[8 * j] != x[0];
+    }
+  if (bad) g->refused = 1;
+  const int full = (1 << g->P) - 1;
+  if (e) {
+    (void)hipMemset(g->err, 0, sizeof(int));
+    // the snapshots run() took, whatever a member's own calls did to its mask since
+    for (ddrl_ctx* c : g->members) {
+      c->snap_mask = full;
+      const int rc = restore_snapshot(c);
+      c->snap_mask = 0;
+      if (rc) return -1;
+    }
+    if (bad)
+      return fail("update group: the workgroups of a chain ran on different XCDs (placement check), so the exchange "
+                  "through the XCD's L2 could not complete.  The weights, Adam state and beta powers of every member "
+                  "are as before the call; this group refuses further runs: update the members one by one");
+    return fail("update group: an exchange between the workgroups of a chain was abandoned (3 s timeout, a grid that "
+                "was not resident, or a failed launch).  The weights, Adam state and beta powers of every member are "
+                "as before the call");
+  }
+  // a stale snapshot must never be restored by a member's later, unrelated check
+  for (ddrl_ctx* c : g->members) c->snap_mask = 0;
+  return 0;
+}
+
+int ddrl_update_group_placement(ddrl_update_group* g, int32_t* xcc, int n_blocks) {
+  if (!g) return fail("null update group");
+  if (!xcc) return fail("null placement buffer");
+  if (g->inflight) return fail("update group: finish the run before reading its placement");
+  if (n_blocks < g->xcc_total)
+    return fail("update group: the placement record holds " + std::to_string(g->xcc_total) +
+                " blocks (the launches' grids, in launch order)");
+  for (int i = 0; i < n_blocks; ++i) xcc[i] = i < g->xcc_total ? g->xcc_host[i] : -1;
+  return 0;
+}
+
+int ddrl_update_group_destroy(ddrl_update_group* g) {
+  if (!g) return 0;
+  (void)hipSetDevice(g->device);
+  (void)hipStreamSynchronize(g->stream);
+  group_free(g);   // (the members may be gone already: they are not touched)
+  return 0;
+}
+
+}  // extern "C"

@@ -313,6 +313,16 @@ void launch_update_ffn_mb256_atomic(hipStream_t s, const UpdateArgs* ua, const U
                                     int own_kq = -1, unsigned lx_base = 0);
 // epoch_ctr: per-context launch counter (granule tags)
 size_t gx_bytes(int P);
+// The group update (ppo_ffn_group.hip): n_chains chains (one policy of one member context each) in
+// one launch of the fused row-split kernel, 128-row minibatches, default protocol, every chain from
+// schedule step 0.  table_dev: device array of n_chains UpdateArgs; xchg: 8 granules per chain,
+// rounded up to whole group rows of 8 chains; gx: gx_bytes(n_chains); xcc: update_group_grid(n_chains)
+// ints; epoch_ctr: the group's launch counter.  Clears the outboxes on the stream first.  Returns
+// -1 (nothing launched) in a library built without the group kernel.
+int update_group_grid(int n_chains);   // blocks of a launch: 32 (rows - 1) + 24 + chains in the last row
+int launch_update_ffn_group(hipStream_t s, const UpdateArgs* table_dev, int n_chains, const UpdateHyper& h, int A, int d,
+                            int stride, int cup, unsigned long long* xchg, unsigned long long* gx, int* err,
+                            unsigned* epoch_ctr, int* xcc);
 // clip_by_global_norm + tf1 Adam on a flat (all-reduced) gradient vector
 // gscale multiplies the gradient before the clip (1 / ranks in the "local" data-parallel mode)
 // err: the context's error word -- a set word (a failed gradient launch) skips the update

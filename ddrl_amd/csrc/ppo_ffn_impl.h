@@ -24,6 +24,17 @@
 #ifndef DDRL_FFN_KSP
 #define DDRL_FFN_KSP 0
 #endif
+// The group unit (ppo_ffn_group.hip, DDRL_FFN_GROUP = 1): the fused row-split kernel of the default
+// protocol at 128 rows with a chain axis -- many contexts' policies in one launch, each chain's
+// UpdateArgs read from a device table (k_update_ffn_group below).  It builds nothing else: no
+// k_update_ffn, no launch_update_ffn.
+#ifndef DDRL_FFN_GROUP
+#define DDRL_FFN_GROUP 0
+#endif
+#if DDRL_FFN_GROUP && (DDRL_FFN_KSP != 2 || DDRL_FFN_AT || DDRL_MB != 128 || defined(DDRL_XCHG_ATOMIC) || \
+                       defined(DDRL_BOUNDS) || defined(DDRL_STAMPS))
+#error "the group unit builds the production fused row-split kernel only (KSP = 2, 128 rows, default protocol)"
+#endif
 // Minibatches of 256 rows (-DDDRL_MB=256 ahead of this header: ppo_ffn_mb256.hip for the default
 // protocol, ppo_ffn_mb256_atomic.hip for the atomic one): only the fused row-split kernels, each
 // workgroup on 128 rows -- two 16-row tiles per wave, the geometry of the split-less A = 8 kernel.
@@ -101,7 +112,9 @@ __host__ __device__ constexpr int gx_pairs(int OB, int NW) {
 #define GX_MAX_PAIRS 20
 
 struct UpdateBatch {
+#if !DDRL_FFN_GROUP   // (the group kernel reads its chains' entries from a device table)
   UpdateArgs a[DDRL_MAXP];   // one entry per policy, by value in the kernel argument block
+#endif
   UpdateHyper h;
   int nrows;             // rows per minibatch handled here (<= DDRL_MB)
   float inv_n;           // 1 / sgd_minibatch_size (global minibatch)
@@ -1529,6 +1542,45 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
   }
 }
 
+#if DDRL_FFN_GROUP
+// The fused row-split update of a group of contexts: chain c (one policy of one member) runs on
+// blocks 32 (c >> 3) + 8 j + (c & 7), j = 2 branch + row half -- k_update_ffn's p + 8 j with a group
+// row every 32 blocks, so a chain's four workgroups stay congruent mod 8 (one XCD) and each XCD
+// holds four workgroups per group row.  Every workgroup spins on partners, so the whole grid must be
+// resident: the host sizes a launch to the device (capi.cpp, ddrl_update_group_create).  The chain's
+// UpdateArgs come from a device table (64 chains do not fit the argument block) through wave-uniform
+// loads; the chain index takes the policy's place in update_loop's outbox and granule indexing, and
+// the step loop is the solo kernel's.
+struct GroupBatch {
+  const UpdateArgs* table;   // [n_chains]
+  int n_chains;
+  UpdateBatch b;             // the scalar fields; xchg / gx / xcc sized for the launch's chains
+};
+template <int A, int KS1, bool CUP>
+__global__ void __launch_bounds__(64 * waves_for(A, 2)) k_update_ffn_group(GroupBatch gb) {
+  extern __shared__ float lds[];
+  constexpr int NW = waves_for(A, 2);
+  const int c = 8 * (int)(blockIdx.x >> 5) + (int)(blockIdx.x & 7);
+  if (threadIdx.x == 0) {   // placement record: XCC of every block (capi.cpp ddrl_update_group_finish)
+    unsigned x;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
+    gb.b.xcc[blockIdx.x] = (int)(x & 0xf);
+  }
+  if (c >= gb.n_chains) return;
+  const int j = (int)(blockIdx.x >> 3) & 3, branch = j >> 1, kq = j & 1;
+  // table[c], word by word into SGPRs (c is a function of blockIdx alone)
+  constexpr int NWORD = (int)(sizeof(UpdateArgs) / sizeof(unsigned));
+  static_assert(sizeof(UpdateArgs) % sizeof(unsigned) == 0, "UpdateArgs in whole words");
+  const unsigned* src = reinterpret_cast<const unsigned*>(gb.table + c);
+  unsigned wd[NWORD];
+#pragma unroll
+  for (int k = 0; k < NWORD; ++k) wd[k] = (unsigned)__builtin_amdgcn_readfirstlane((int)src[k]);
+  UpdateArgs U;
+  __builtin_memcpy(&U, wd, sizeof(U));
+  if (branch) update_loop<A, KS1, 1, false, NW, 2, false, true>(U, gb.b, lds, c, kq);
+  else update_loop<A, KS1, 2 * A, true, NW, 2, CUP, true>(U, gb.b, lds, c, kq);
+}
+#else
 template <int A, int KS1, int KSP, bool CUP, bool LSBX>
 __global__ void __launch_bounds__(64 * waves_for(A, KSP)) k_update_ffn(UpdateBatch ub) {
   extern __shared__ float lds[];
@@ -1550,6 +1602,8 @@ __global__ void __launch_bounds__(64 * waves_for(A, KSP)) k_update_ffn(UpdateBat
   else update_loop<A, KS1, 2 * A, true, NW, KSP, CUP, LSBX>(U, ub, lds, p, kq);
 }
 
+#endif   // !DDRL_FFN_GROUP
+
 // stride: the widest record stride of the launched policies (staging buffer rows)
 static size_t update_lds_bytes(int O, int stride, int ksp) {
   const int nsb = 64 * O + O + 128 + ncup_slots(O, true);
@@ -1560,6 +1614,48 @@ static size_t update_lds_bytes(int O, int stride, int ksp) {
                   (DDRL_MB / ksp) * 4 * stg_chunks(stride, O / 2)) * 4;
 }
 
+#if DDRL_FFN_GROUP
+template <int A, int KS1, bool CUP = false>
+static void launch_group_t(hipStream_t s, GroupBatch& gb, int stride, int grid) {
+  gb.b.lds_bytes = (unsigned)update_lds_bytes(2 * A, stride, 2);
+  hipLaunchKernelGGL((k_update_ffn_group<A, KS1, CUP>), dim3(grid), dim3(64 * waves_for(A, 2)), gb.b.lds_bytes, s, gb);
+}
+
+}  // namespace
+
+int update_group_grid(int n_chains) { return 32 * ((n_chains - 1) >> 3) + 24 + ((n_chains - 1) & 7) + 1; }
+
+int launch_update_ffn_group(hipStream_t s, const UpdateArgs* table_dev, int n_chains, const UpdateHyper& h, int A, int d,
+                            int stride, int cup, unsigned long long* xchg, unsigned long long* gx, int* err,
+                            unsigned* epoch_ctr, int* xcc) {
+  if (n_chains < 1) return -1;
+  GroupBatch gb;
+  gb.table = table_dev;
+  gb.n_chains = n_chains;
+  gb.b.h = h;
+  gb.b.nrows = DDRL_MB;
+  gb.b.inv_n = 1.f / DDRL_MB;
+  gb.b.xchg = xchg;
+  gb.b.gx = gx;
+  gb.b.err = err;
+  gb.b.xcc = xcc;
+  gb.b.own_kq = -1;
+  gb.b.lx_base = 0;
+  // the group's own launch epoch (12 bits, never 0) tags the norm granules, which are cleared when
+  // it wraps; the quads' outboxes start cleared in every launch (schedule step 0: both parities'
+  // first tag bit is 1, so zero words never match), as in DDRL_FFN_LAUNCH
+  gb.b.epoch = (*epoch_ctr)++ % 4095u + 1u;
+  const int rows8 = 8 * ((n_chains + 7) >> 3);
+  if (gb.b.epoch == 1) (void)hipMemsetAsync(xchg, 0, sizeof(unsigned long long) * 8 * (size_t)rows8, s);
+  (void)hipMemsetAsync(gx, 0, gx_bytes(n_chains), s);
+  const int grid = update_group_grid(n_chains);
+  if (cup)
+    launch_group_t<2, 5, true>(s, gb, stride, grid);
+  else
+    DDRL_DISPATCH_A_KS1(A, d, launch_group_t, s, gb, stride, grid);
+  return 0;
+}
+#else
 template <int A, int KS1, bool CUP = false>
 static void launch_update_t(hipStream_t s, UpdateBatch& ub, int P, int stride, int ksp, bool lx) {
   ub.lds_bytes = (unsigned)update_lds_bytes(2 * A, stride, ksp);
@@ -1642,3 +1738,4 @@ void DDRL_FFN_LAUNCH(hipStream_t s, const UpdateArgs* ua, const UpdateHyper& h, 
   else
     DDRL_DISPATCH_A_KS1(A, d, launch_update_t, s, ub, h.P, stride, ksp, lx);
 }
+#endif   // !DDRL_FFN_GROUP

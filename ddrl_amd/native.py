@@ -174,6 +174,12 @@ _SIGS = {
     "ddrl_episodes_rows": ([VP, VP, C.c_size_t], C.c_int),
     "ddrl_episodes_inflight": ([VP, VP, C.c_size_t], C.c_int),
     "ddrl_episodes_reset": ([VP], C.c_int),
+    "ddrl_update_group_create": ([C.POINTER(VP), C.c_int, C.c_int, C.POINTER(VP)], C.c_int),
+    "ddrl_update_group_run": ([VP, C.POINTER(VP), C.POINTER(VP), C.POINTER(f32), C.c_int], C.c_int),
+    "ddrl_update_group_finish": ([VP], C.c_int),
+    "ddrl_update_group_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32)], C.c_int),
+    "ddrl_update_group_placement": ([VP, C.POINTER(i32), C.c_int], C.c_int),
+    "ddrl_update_group_destroy": ([VP], C.c_int),
 }
 
 _lib = None
@@ -669,6 +675,81 @@ def _terrain_points(env_index, xy, n_envs):
     if idx.size and (idx.min() < 0 or idx.max() >= n_envs):
         raise DdrlError(f"terrain_height: env index out of range [0, {n_envs})")
     return idx, pts
+
+
+def update_group_grid(n_chains):
+    """Blocks of a group launch of n_chains chains: 32 per full group row of 8, 24 + chains in the last."""
+    rows = (n_chains + 7) // 8
+    return 32 * (rows - 1) + 24 + (n_chains - 8 * (rows - 1))
+
+
+def update_group_plan(n_members, n_policies, max_chains):
+    """ddrl_update_group_plan (pure host, no GPU): (launch_of_member[M], first_block_of_chain[M, P]) for
+    launches of at most max_chains chains; chain (m, p) runs on blocks first_block + 8 j, j = 0 .. 3,
+    of its launch's grid."""
+    lom = (i32 * max(1, n_members))()
+    fb = (i32 * max(1, n_members * n_policies))()
+    _ck(load().ddrl_update_group_plan(n_members, n_policies, max_chains, lom, fb))
+    return (np.array(lom[:n_members], np.int32),
+            np.array(fb[:n_members * n_policies], np.int32).reshape(n_members, n_policies))
+
+
+class UpdateGroup:
+    """The fused updates of several same-shaped contexts in one launch (a ddrl_update_group): every
+    member's chains bit-identical to its own Context.ppo_update.  Close the group before its members."""
+
+    def __init__(self, contexts, max_chains_per_launch=0):
+        self.lib = load()
+        self.contexts = list(contexts)
+        self.P = self.contexts[0].cfg.n_policies if self.contexts else 0
+        hs = (VP * max(1, len(self.contexts)))(*[c.h for c in self.contexts])
+        h = VP()
+        _ck(self.lib.ddrl_update_group_create(hs, len(self.contexts), max_chains_per_launch, C.byref(h)))
+        self.h = h
+
+    def _h(self):
+        if not getattr(self, "h", None):
+            raise DdrlError("update group: used after close")
+        return self.h
+
+    def run(self, shuffles, perms, kl_coeffs, max_steps=-1):
+        """shuffles / perms / kl_coeffs: one list per member, one entry per policy; asynchronous."""
+        h = self._h()
+        n = len(self.contexts) * self.P
+        flat = lambda xs: [x for member in xs for x in list(member)[:self.P]]
+        sh, pe, kl = flat(shuffles), flat(perms), flat(kl_coeffs)
+        if not (len(sh) == len(pe) == len(kl) == n):
+            raise DdrlError(f"update group: {n} (member, policy) entries expected")
+        self._keep = (sh, pe)   # the device schedules stay alive until the run is finished
+        _ck(self.lib.ddrl_update_group_run(h, (VP * n)(*[_ptr(x) for x in sh]), (VP * n)(*[_ptr(x) for x in pe]),
+                                           (f32 * n)(*[float(k) for k in kl]), max_steps))
+
+    def finish(self):
+        """Synchronize and check; on failure every member is as before the run and DdrlError is raised."""
+        try:
+            _ck(self.lib.ddrl_update_group_finish(self._h()))
+        finally:
+            self._keep = None
+
+    def placement(self):
+        """XCC id of every block of the last finished run: the launches' grids in launch order, one flat
+        array (update_group_plan and update_group_grid give each launch's share)."""
+        n = 32 * max(1, len(self.contexts) * self.P)   # a launch of n chains has at most 32 n blocks
+        x = (i32 * n)()
+        _ck(self.lib.ddrl_update_group_placement(self._h(), x, n))
+        a = np.array(x[:], np.int32)
+        return a[:int((a >= 0).sum())]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ddrl_update_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class HostEnv:

@@ -1,0 +1,78 @@
+"""Train several seeds of one experiment side by side.
+
+A single run's fused PPO update is four sequential chains on 16 of the device's CUs, and it is
+nearly the whole cost of an iteration.  The seeds of one experiment are independent runs of the
+same shape, so their updates fit one launch (native.UpdateGroup, csrc/ppo_ffn_group.hip): member
+m of a PopulationTrainer is, bit for bit, the solo PPOTrainer(config, seed=seeds[m]) -- its own
+context, envs, noise, schedule, filters, KL coefficients and results -- with the M update launches
+of an iteration replaced by one.  Sampling stays per member, in stream order.
+"""
+from __future__ import annotations
+
+import os
+import time
+
+from . import native as N
+from .trainer import PPOTrainer
+
+
+class PopulationTrainer:
+    """M PPOTrainers on one device and stream, updated by one group launch per iteration.
+
+    max_chains_per_launch: 0 = as many chains (members x policies) per launch as the device holds
+    resident; a smaller value splits the update into several launches of whole members (the same
+    results).  fcnet models, sgd_minibatch_size 128 and single-process replicas only: anything the
+    group update refuses raises here, with its reason.
+    """
+
+    def __init__(self, config, seeds, n_envs=None, device=0, max_chains_per_launch=0):
+        import torch
+        self.torch = torch
+        self.seeds = [int(s) for s in seeds]
+        torch.cuda.set_device(device)
+        self.device = torch.device("cuda", device)
+        self.stream = torch.cuda.current_stream(self.device)
+        self.trainers = []
+        self.group = None
+        try:
+            for s in self.seeds:
+                self.trainers.append(PPOTrainer(config, n_envs=n_envs, device=device, seed=s, stream=self.stream))
+            for t in self.trainers:
+                if t.world != 1 or t.parallel != "replicas":
+                    raise ValueError(f"PopulationTrainer: parallel {t.parallel!r} over {t.world} process(es); a "
+                                     "population is single-process replicas")
+            self.group = N.UpdateGroup([t.ctx for t in self.trainers], max_chains_per_launch)
+        except Exception:
+            self.stop()
+            raise
+
+    def train(self):
+        """One iteration of every member; the list of the members' result dicts."""
+        t0 = time.perf_counter()
+        for t in self.trainers:
+            t._sample()
+        self.torch.cuda.synchronize(self.device)
+        t1 = time.perf_counter()
+        sched = [t._learn_schedules() for t in self.trainers]
+        self.group.run([s[0] for s in sched], [s[1] for s in sched], [t.kl_coeff for t in self.trainers])
+        self.group.finish()
+        learners = [t._learn_results(s[2]) for t, s in zip(self.trainers, sched)]
+        t2 = time.perf_counter()
+        return [t._iteration_result(lr, t0, t1, t2) for t, lr in zip(self.trainers, learners)]
+
+    def save(self, directory):
+        """One npz checkpoint per member, seed_<seed>.npz under `directory`; the paths."""
+        os.makedirs(directory, exist_ok=True)
+        return [t.save(os.path.join(directory, f"seed_{s}.npz")) for t, s in zip(self.trainers, self.seeds)]
+
+    def restore(self, directory):
+        for t, s in zip(self.trainers, self.seeds):
+            t.restore(os.path.join(directory, f"seed_{s}.npz"))
+
+    def stop(self):
+        if self.group is not None:   # before its members
+            self.group.close()
+            self.group = None
+        for t in self.trainers:
+            t.stop()
+        self.trainers = []

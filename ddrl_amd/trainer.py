@@ -292,15 +292,26 @@ class PPOTrainer:
             return self._learn_ddp()
         if self.parallel == "gather":
             self._gather_records()
+        sh, pe, nbs = self._learn_schedules()
+        self.ctx.ppo_update((1 << self.cfg.n_policies) - 1, sh, pe, self.kl_coeff)
+        return self._learn_results(nbs)
+
+    def _learn_schedules(self):
+        """The part of the fused update before its launch: every policy's schedule on the device,
+        drawn from this trainer's sched_rng in policy order.  (shuffles, perms, minibatches per epoch)"""
         torch = self.torch
-        P = self.cfg.n_policies
         sh, pe, nbs = [], [], []
-        for p in range(P):
+        for p in range(self.cfg.n_policies):
             s, q, nb = self._schedule(p)
             sh.append(torch.from_numpy(s).to(self.device))
             pe.append(torch.from_numpy(q).to(self.device))
             nbs.append(nb)
-        self.ctx.ppo_update((1 << P) - 1, sh, pe, self.kl_coeff)
+        return sh, pe, nbs
+
+    def _learn_results(self, nbs):
+        """The part after the launch (this trainer's own, or a group's: ddrl_amd.population): the last
+        epoch's statistics, update_kl and the learner dict."""
+        P = self.cfg.n_policies
         learner = {}
         for p, pid in enumerate(self.policy_ids):
             st = self.ctx.ppo_stats(p, nbs[p], first=(self.cfg.num_sgd_iter - 1) * nbs[p])
@@ -323,7 +334,11 @@ class PPOTrainer:
         torch.cuda.synchronize(self.device)
         t1 = time.perf_counter()
         learner = self._learn()
-        t2 = time.perf_counter()
+        return self._iteration_result(learner, t0, t1, time.perf_counter())
+
+    def _iteration_result(self, learner, t0, t1, t2):
+        """The end of an iteration: counters, callback and RLlib's result dict.  t0 / t1 / t2: start,
+        end of sampling, end of learning."""
         steps = self.T * self.n_envs
         self.timesteps_total += steps
         self.iteration += 1

@@ -465,6 +465,50 @@ int ddrl_ppo_stats(ddrl_ctx* ctx, int pid, float* host, size_t n_steps);
  * (3p ppo.py update_kl, on the last epoch's mean KL) need only the last epoch's nb rows. */
 int ddrl_ppo_stats_range(ddrl_ctx* ctx, int pid, size_t first, size_t n_steps, float* host);
 
+/* Group update: the fused PPO updates of M contexts of one shape -- e.g. the seeds of one
+ * experiment -- in one launch.  One run's chains cannot be widened (four sequential chains on 16
+ * CUs), several runs' chains are independent: chain m * n_policies + p (policy p of member m)
+ * runs on blocks 32 (c >> 3) + 8 j + (c & 7) of its launch, c its index in the launch, j = 0 .. 3 (policy / value branch x
+ * row half), so the four workgroups of a chain share an XCD as a context's do.  Every member stays
+ * a full, ordinary context (its own records, schedule, weights, Adam state, KL coefficients), and
+ * each chain computes, bit for bit, what ddrl_ppo_update on its context alone computes.  fcnet
+ * models, sgd_minibatch_size 128, the row split and the default exchange protocol only.
+ *   create: members[n_members], all on one device and one stream (the group enqueues on it).
+ *     Refuses, naming the member and the reason: no member, a null or repeated context, another
+ *     device or stream, a ddrl_cfg that differs from member 0's in anything the update reads, a
+ *     GraphNet member, sgd_minibatch_size 256, DDRL_UPDATE_SPLIT=1, the atomic protocol, an attached
+ *     peer.  max_chains_per_launch: 0 = the device's cap, 8 * floor((CUs / 8) / 4) chains (all
+ *     workgroups of a launch spin on partners and must be resident, one per CU: 64 chains on an
+ *     MI355X); a group with more chains, or a smaller value here, runs as several launches in
+ *     stream order, whole members per launch, with the same results.  The group owns the argument
+ *     table (device, filled from a pinned host buffer), the exchange arenas, its error word, its
+ *     launch epoch and the per-block XCC record.  Destroy the group before its members.
+ *   run: ddrl_ppo_update for every policy of every member from schedule step 0: shuffle_dev /
+ *     perm_dev / kl_coeff hold n_members * n_policies entries, member-major; max_steps is common.
+ *     Takes each member's snapshot; ddrl_ppo_stats* on a member afterwards work unchanged.
+ *     Asynchronous; one run at a time (finish it before the next).
+ *   finish: synchronizes and checks.  On failure (an exchange abandoned after 3 s -- e.g. a grid
+ *     that was not resident -- or a failed launch) every member's snapshot is restored and the
+ *     message says so.  When a chain's four blocks ran on different XCDs the message names the
+ *     placement check and the group refuses further runs: update the members one by one.
+ *   plan: pure host function (no GPU): launch_of_member[n_members] and
+ *     first_block_of_chain[n_members * n_policies] (the chain's block 8 j apart, in its launch's
+ *     grid) for launches of at most max_chains chains.  A launch of n chains has
+ *     32 (ceil(n / 8) - 1) + 24 + (n - 8 (ceil(n / 8) - 1)) blocks.
+ *   placement: after finish; the XCC id of every block of the last run, the launches' grids in
+ *     launch order; n_blocks >= their sum, the entries past it are set to -1 (-1 too for a run
+ *     that has not finished yet). */
+typedef struct ddrl_update_group ddrl_update_group;
+int ddrl_update_group_create(ddrl_ctx* const* members, int n_members, int max_chains_per_launch,
+                             ddrl_update_group** out);
+int ddrl_update_group_run(ddrl_update_group* group, const int32_t* const* shuffle_dev,
+                          const int32_t* const* perm_dev, const float* kl_coeff, int max_steps);
+int ddrl_update_group_finish(ddrl_update_group* group);
+int ddrl_update_group_plan(int n_members, int n_policies, int max_chains, int32_t* launch_of_member,
+                           int32_t* first_block_of_chain);
+int ddrl_update_group_placement(ddrl_update_group* group, int32_t* xcc, int n_blocks);
+int ddrl_update_group_destroy(ddrl_update_group* group);
+
 /* Data-parallel (shared policy) primitives: gradient of (1/minibatch) * sum over the
  * given rows -> grad_dev[n_params]; after the caller's all-reduce (RCCL), apply clip +
  * Adam.  rows_dev holds n_rows (<= 128) record indices.  stats_step >= 0 also writes this
