@@ -2588,3 +2588,199 @@ int ddrl_update_group_destroy(ddrl_update_group* g) {
 }
 
 }  // extern "C"
+
+// ---- group rollout (rollout_group.hip): the device-plane fragments of M same-shaped contexts as one chain ----
+// Member m is the context members[m] with its own device env plane envs[m].  The kernels read what
+// differs between members from a device table of RolloutMember, rebuilt at every run from the
+// members' current state (so terrain, time limit and target velocities set between runs hold) in
+// a pinned host buffer the group owns, and copied on the stream; `copied` is recorded behind that
+// copy and waited on before the buffer is rewritten.
+struct ddrl_rollout_group {
+  std::vector<ddrl_ctx*> members;
+  std::vector<ddrl_devenv*> envs;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  RolloutMember* table_host = nullptr;   // pinned
+  RolloutMember* table_dev = nullptr;
+  hipEvent_t copied = nullptr;
+  int copy_pending = 0;
+};
+
+namespace {
+std::string rmember_name(int m) { return "rollout group: member " + std::to_string(m); }
+
+// the reward tables without what is per member (the record pointers)
+RewardArgs shape_reward(ddrl_ctx* c) {
+  RewardArgs r = make_reward(c);
+  for (int p = 0; p < DDRL_MAXP; ++p) r.rec[p] = nullptr;
+  return r;
+}
+
+// the first difference between member m's configuration and member 0's in anything the rollout kernels read
+int rgroup_same_shape(ddrl_ctx* a, ddrl_ctx* b, int m) {
+  const ddrl_cfg &x = a->cfg, &y = b->cfg;
+  const char* why = nullptr;
+#define DDRL_RGRP_SAME(f) if (!why && !(x.f == y.f)) why = #f
+  DDRL_RGRP_SAME(model_kind); DDRL_RGRP_SAME(n_envs); DDRL_RGRP_SAME(frag_len); DDRL_RGRP_SAME(n_policies);
+  DDRL_RGRP_SAME(n_agents); DDRL_RGRP_SAME(act_dim); DDRL_RGRP_SAME(obs_full_dim); DDRL_RGRP_SAME(leg_coupling);
+  DDRL_RGRP_SAME(policy_filter); DDRL_RGRP_SAME(filter_enabled); DDRL_RGRP_SAME(filter_update);
+  DDRL_RGRP_SAME(filter_clip); DDRL_RGRP_SAME(reward_mode); DDRL_RGRP_SAME(ctrl_cost_weight);
+  DDRL_RGRP_SAME(contact_cost_weight);
+#undef DDRL_RGRP_SAME
+  for (int p = 0; p < x.n_policies && !why; ++p) {
+    const Policy &P = a->pol[p], &Q = b->pol[p];
+    if (P.d != Q.d) why = "obs_dim";
+    else if (P.k != Q.k) why = "agent_policy (agents per policy)";
+    else if (std::memcmp(&P.lay, &Q.lay, sizeof(RecLayout)) != 0) why = "the record layout";
+  }
+  if (!why && std::memcmp(&a->route, &b->route, sizeof(RouteArgs)) != 0)
+    why = "the routing tables (agent_policy, obs_index, act_index, act_negate, leg angles)";
+  if (!why) {
+    const RewardArgs ra = shape_reward(a), rb = shape_reward(b);
+    if (std::memcmp(&ra, &rb, sizeof(RewardArgs)) != 0) why = "the reward tables (n_contact, contact_index, contact_weight)";
+  }
+  if (why) return fail(rmember_name(m) + " differs from member 0 in " + why + ": a group takes contexts of one shape");
+  return 0;
+}
+
+// what a member and its env must still be at every run (create checks it too)
+int rgroup_member_ok(const ddrl_rollout_group* g, int m) {
+  const ddrl_ctx* c = g->members[m];
+  const ddrl_devenv *e = g->envs[m], *e0 = g->envs[0];
+  if (!e->ctx) return fail(rmember_name(m) + ": its device env's context has been destroyed");
+  if (e->ctx != c) return fail(rmember_name(m) + ": its device env is bound to another context");
+  if (c->stream != g->stream) return fail(rmember_name(m) + " is on another stream than member 0");
+  if (e->a.ter_on != e0->a.ter_on)
+    return fail(rmember_name(m) + " has its terrain " + (e->a.ter_on ? "on" : "off") + " and member 0 " +
+                (e0->a.ter_on ? "on" : "off") + ": the step kernel's instance is one per launch");
+  if (!e->a.tv_env != !e0->a.tv_env)
+    return fail(rmember_name(m) + " and member 0 differ in the target-velocity mode (a per-env table against draws from "
+                "the list): the step kernel's instance is one per launch");
+  return 0;
+}
+
+void rgroup_free(ddrl_rollout_group* g) {
+  if (g->copied) (void)hipEventDestroy(g->copied);
+  if (g->table_host) (void)hipHostFree(g->table_host);
+  if (g->table_dev) (void)hipFree(g->table_dev);
+  delete g;
+}
+}  // namespace
+
+extern "C" {
+
+int ddrl_rollout_group_create(ddrl_ctx* const* members, ddrl_devenv* const* envs, int n_members,
+                              ddrl_rollout_group** out) {
+  if (!members || !envs || !out) return fail("null argument");
+  if (n_members < 1) return fail("rollout group: at least one member is needed");
+  if (n_members > 65535)
+    return fail("rollout group: " + std::to_string(n_members) + " members exceed the grid's z extent (65535)");
+  for (int m = 0; m < n_members; ++m) {
+    if (!members[m]) return fail(rmember_name(m) + " is a null context");
+    if (!envs[m]) return fail(rmember_name(m) + " has a null device env");
+    for (int k = 0; k < m; ++k) {
+      if (members[k] == members[m]) return fail(rmember_name(m) + " repeats member " + std::to_string(k));
+      if (envs[k] == envs[m]) return fail(rmember_name(m) + " repeats the device env of member " + std::to_string(k));
+    }
+  }
+  ddrl_ctx* c0 = members[0];
+  HIPCHK(hipSetDevice(c0->device));
+  ddrl_rollout_group* g = new ddrl_rollout_group();
+  g->members.assign(members, members + n_members);
+  g->envs.assign(envs, envs + n_members);
+  g->device = c0->device;
+  g->stream = c0->stream;
+  int rc = 0;
+  for (int m = 0; m < n_members && !rc; ++m) {
+    ddrl_ctx* c = members[m];
+    if (c->device != g->device) rc = fail(rmember_name(m) + " is on another device than member 0");
+    else if (c->cfg.model_kind != DDRL_MODEL_FFN) rc = fail(rmember_name(m) + " is a GraphNet context: the group rollout runs the fcnet kernels only");
+    else rc = rgroup_same_shape(c, c0, m);
+  }
+  for (int m = 0; m < n_members && !rc; ++m) rc = rgroup_member_ok(g, m);
+  if (!rc) {
+    const size_t bytes = sizeof(RolloutMember) * (size_t)n_members;
+    if (hipHostMalloc((void**)&g->table_host, bytes, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc((void**)&g->table_dev, bytes) != hipSuccess || hipMemset(g->table_dev, 0, bytes) != hipSuccess ||
+        hipEventCreateWithFlags(&g->copied, hipEventDisableTiming) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      rc = fail("rollout group: allocation of the member table failed");
+  }
+  if (rc) {
+    rgroup_free(g);
+    return -1;
+  }
+  *out = g;
+  return 0;
+}
+
+int ddrl_rollout_group_run(ddrl_rollout_group* g, const float* const* eps_dev, int reset) {
+  if (!g) return fail("null rollout group");
+  if (!eps_dev) return fail("null noise buffer");
+  const int M = (int)g->members.size();
+  for (int m = 0; m < M; ++m) {
+    if (!eps_dev[m]) return fail(rmember_name(m) + ": null noise buffer");
+    if (rgroup_member_ok(g, m)) return -1;
+  }
+  HIPCHK(hipSetDevice(g->device));
+  ddrl_ctx* c0 = g->members[0];
+  const ddrl_cfg& cfg = c0->cfg;
+  if (reset)
+    for (int m = 0; m < M; ++m)
+      if (ddrl_devenv_reset(g->envs[m]) || ddrl_observe(g->members[m], g->envs[m]->a.obs)) return -1;
+  // the pinned table is the source of the previous run's H2D copy: wait for that copy before rewriting it
+  if (g->copy_pending) {
+    HIPCHK(hipEventSynchronize(g->copied));
+    g->copy_pending = 0;
+  }
+  for (int m = 0; m < M; ++m) {
+    ddrl_ctx* c = g->members[m];
+    RolloutMember& r = g->table_host[m];
+    r = RolloutMember{};
+    for (int p = 0; p < cfg.n_policies; ++p) {
+      Policy& P = c->pol[p];
+      r.theta[p] = P.theta; r.stage[p] = P.stage; r.rec[p] = P.rec; r.last_v[p] = P.last_v;
+      r.cup[p] = cup_table(c, p);
+    }
+    r.eps = eps_dev[m]; r.actions = c->h_act; r.done_tn = c->done_tn;
+    r.f_n = c->f_n; r.f_M = c->f_M; r.f_S = c->f_S; r.f_normc = c->f_normc;
+    r.f_dn = c->f_dn; r.f_dM = c->f_dM; r.f_dS = c->f_dS; r.f_part = c->f_part;
+    r.pf = cfg.policy_filter ? c->pf : nullptr;
+    r.zs = c->zs;
+    r.env = g->envs[m]->a;
+  }
+  HIPCHK(hipMemcpyAsync(g->table_dev, g->table_host, sizeof(RolloutMember) * (size_t)M, hipMemcpyHostToDevice, g->stream));
+  HIPCHK(hipEventRecord(g->copied, g->stream));
+  g->copy_pending = 1;
+  RolloutGroupArgs ga{};
+  ga.tab = g->table_dev; ga.M = M; ga.n = cfg.n_envs; ga.T = cfg.frag_len;
+  for (int p = 0; p < cfg.n_policies; ++p) {
+    ga.lay[p] = c0->pol[p].lay;
+    ga.C[p] = c0->pol[p].C;
+  }
+  ga.filter_update = cfg.filter_update; ga.filter_enabled = cfg.filter_enabled; ga.policy_filter = cfg.policy_filter;
+  ga.clip = effective_clip(cfg);
+  ga.ter_on = g->envs[0]->a.ter_on; ga.tv_env = g->envs[0]->a.tv_env ? 1 : 0;
+  const RewardArgs rw = shape_reward(c0);
+  // issued directly: the same chain as one replayed HIP graph was no faster (DESIGN.md section 3,
+  // "Population rollout"; profiles/population/rollout_graph_ab.json)
+  for (int t = 0; t < cfg.frag_len; ++t) launch_rollout_group_step(g->stream, c0->route, rw, ga, t);
+  launch_rollout_group_bootstrap(g->stream, c0->route, ga);
+  HIPCHK(hipGetLastError());
+  // what the plain calls would have noted on every member
+  for (ddrl_ctx* c : g->members) {
+    c->ep_collected = 0;
+    c->ev_normc_ok = 0;
+    c->sens_act_ok = 0;
+  }
+  return 0;
+}
+
+int ddrl_rollout_group_destroy(ddrl_rollout_group* g) {
+  if (!g) return 0;
+  (void)hipSetDevice(g->device);
+  (void)hipStreamSynchronize(g->stream);
+  rgroup_free(g);   // (the members may be gone already: they are not touched)
+  return 0;
+}
+
+}  // extern "C"

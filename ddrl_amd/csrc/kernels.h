@@ -258,6 +258,39 @@ void launch_devenv_reset(hipStream_t s, const DevEnvArgs& a, int mode);
 // packed[N][41] (DDRL_ENV_STATE_DOUBLES) <- state, or state <- packed when unpack
 void launch_devenv_pack(hipStream_t s, const DevEnvArgs& a, double* packed, int unpack);
 
+// ---- group rollout (rollout_group.hip): the device-plane fragments of M contexts side by side ----
+// Member m is a context and its device env plane, separately allocated: everything that differs
+// between members is one RolloutMember in a device table, indexed by blockIdx.z (wave-uniform);
+// what is equal for all (routing, reward tables, record layout, sizes) goes by value.
+struct RolloutMember {
+  const float* theta[DDRL_MAXP];
+  float* stage[DDRL_MAXP];
+  float* rec[DDRL_MAXP];
+  const float* cup[DDRL_MAXP];     // "cup" leg-coupling table [4][A] (nullptr: none)
+  float* last_v[DDRL_MAXP];
+  const float* eps;                // [T][n][n_agents][A] noise of the fragment
+  float* actions;                  // [n][8]
+  uint8_t* done_tn;                // [T][n]
+  double *f_n, *f_M, *f_S, *f_normc, *f_dn, *f_dM, *f_dS, *f_part;   // env-side filter and its chunk scratch
+  double* pf;                      // per-policy filter state [P][PF_STRIDE] (nullptr: disabled)
+  double* zs;
+  DevEnvArgs env;                  // the member's env plane: state, outputs, seed, time limit, velocities, terrain
+};
+struct RolloutGroupArgs {
+  const RolloutMember* tab;        // device table of M members
+  int M, n, T;                     // members, envs per member, fragment length
+  RecLayout lay[DDRL_MAXP];
+  int C[DDRL_MAXP];                // rows per step of each policy (n * k)
+  int filter_update, filter_enabled, policy_filter;
+  float clip;                      // effective clip of the env-side filter (0: none)
+  int ter_on, tv_env;              // the step kernel's instance (equal for all members)
+};
+// one env step of every member: act(t) -> env step -> reward(t) -> filter push -> (policy filter) ->
+// observe, the launch order of a plain device-plane step.  rw: the reward tables (rec / t unused / set here)
+void launch_rollout_group_step(hipStream_t s, const RouteArgs& ra, const RewardArgs& rw, const RolloutGroupArgs& ga, int t);
+// V(s_T) of every member into last_v
+void launch_rollout_group_bootstrap(hipStream_t s, const RouteArgs& ra, const RolloutGroupArgs& ga);
+
 // ---- PPO update (fused persistent minibatch loop) ----
 struct UpdateArgs {
   const float* rec; RecLayout lay;

@@ -180,6 +180,9 @@ _SIGS = {
     "ddrl_update_group_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32)], C.c_int),
     "ddrl_update_group_placement": ([VP, C.POINTER(i32), C.c_int], C.c_int),
     "ddrl_update_group_destroy": ([VP], C.c_int),
+    "ddrl_rollout_group_create": ([C.POINTER(VP), C.POINTER(VP), C.c_int, C.POINTER(VP)], C.c_int),
+    "ddrl_rollout_group_run": ([VP, C.POINTER(VP), C.c_int], C.c_int),
+    "ddrl_rollout_group_destroy": ([VP], C.c_int),
 }
 
 _lib = None
@@ -743,6 +746,46 @@ class UpdateGroup:
     def close(self):
         if getattr(self, "h", None):
             self.lib.ddrl_update_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RolloutGroup:
+    """The device-plane fragments of several same-shaped contexts as one chain of launches (a
+    ddrl_rollout_group): member m = (contexts[m], envs[m]), bit-identical to its own
+    Context.rollout_devenv.  Close the group before its members and their envs."""
+
+    def __init__(self, contexts, envs):
+        self.lib = load()
+        self.contexts, self.envs = list(contexts), list(envs)
+        if len(self.contexts) != len(self.envs):
+            raise DdrlError(f"rollout group: {len(self.contexts)} contexts and {len(self.envs)} device envs")
+        n = len(self.contexts)
+        cs = (VP * max(1, n))(*[c.h for c in self.contexts])
+        es = (VP * max(1, n))(*[e.h for e in self.envs])
+        h = VP()
+        _ck(self.lib.ddrl_rollout_group_create(cs, es, n, C.byref(h)))
+        self.h = h
+
+    def run(self, eps_devs, reset=False):
+        """eps_devs: one [T, N, n_agents, A] float32 device tensor per member; asynchronous, on the
+        members' stream."""
+        if not getattr(self, "h", None):
+            raise DdrlError("rollout group: used after close")
+        eps = list(eps_devs)
+        if len(eps) != len(self.contexts):
+            raise DdrlError(f"rollout group: {len(self.contexts)} noise buffers expected")
+        _ck(self.lib.ddrl_rollout_group_run(self.h, (VP * max(1, len(eps)))(*[_ptr(x) for x in eps]),
+                                            1 if reset else 0))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ddrl_rollout_group_destroy(self.h)
             self.h = None
 
     def __del__(self):

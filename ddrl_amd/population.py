@@ -5,7 +5,10 @@ nearly the whole cost of an iteration.  The seeds of one experiment are independ
 same shape, so their updates fit one launch (native.UpdateGroup, csrc/ppo_ffn_group.hip): member
 m of a PopulationTrainer is, bit for bit, the solo PPOTrainer(config, seed=seeds[m]) -- its own
 context, envs, noise, schedule, filters, KL coefficients and results -- with the M update launches
-of an iteration replaced by one.  Sampling stays per member, in stream order.
+of an iteration replaced by one.  On the device env plane the members' fragments are one chain of
+launches too (native.RolloutGroup, csrc/rollout_group.hip), each member drawing its noise from its
+own generator as the solo trainer does; GAE and the episode accounting stay per member.  On the
+synthetic and host planes sampling stays per member, in stream order.
 """
 from __future__ import annotations
 
@@ -23,9 +26,12 @@ class PopulationTrainer:
     resident; a smaller value splits the update into several launches of whole members (the same
     results).  fcnet models, sgd_minibatch_size 128 and single-process replicas only: anything the
     group update refuses raises here, with its reason.
+    group_rollout: None = the members' fragments as one group chain when every member runs the device
+    env plane (env_backend "device"), member by member otherwise; True = the group chain, or an error
+    with the reason; False = member by member.  The results are the same bit for bit.
     """
 
-    def __init__(self, config, seeds, n_envs=None, device=0, max_chains_per_launch=0):
+    def __init__(self, config, seeds, n_envs=None, device=0, max_chains_per_launch=0, group_rollout=None):
         import torch
         self.torch = torch
         self.seeds = [int(s) for s in seeds]
@@ -34,6 +40,7 @@ class PopulationTrainer:
         self.stream = torch.cuda.current_stream(self.device)
         self.trainers = []
         self.group = None
+        self.rollout_group = None
         try:
             for s in self.seeds:
                 self.trainers.append(PPOTrainer(config, n_envs=n_envs, device=device, seed=s, stream=self.stream))
@@ -42,15 +49,47 @@ class PopulationTrainer:
                     raise ValueError(f"PopulationTrainer: parallel {t.parallel!r} over {t.world} process(es); a "
                                      "population is single-process replicas")
             self.group = N.UpdateGroup([t.ctx for t in self.trainers], max_chains_per_launch)
+            self._init_group_rollout(group_rollout)
         except Exception:
             self.stop()
             raise
 
+    def _init_group_rollout(self, group_rollout):
+        """group_rollout None: the group rollout when every member runs the device env plane, the
+        member-by-member sampling otherwise; True: the group rollout or an error with the reason;
+        False: member by member."""
+        from .envs import DeviceVecEnv
+        on_device = bool(self.trainers) and all(isinstance(t.backend, DeviceVecEnv) for t in self.trainers)
+        if group_rollout is None:
+            group_rollout = on_device
+        if not group_rollout:
+            return
+        if not on_device:
+            raise ValueError("PopulationTrainer: group_rollout needs every member on the device env plane "
+                             "(env_backend: 'device'); the synthetic and host planes sample member by member")
+        self.rollout_group = N.RolloutGroup([t.rctx for t in self.trainers], [t.backend.env for t in self.trainers])
+        # every member's noise of a fragment, [T, n_envs, n_agents, A]: filled step by step from the
+        # member's own generator (the solo trainer's draw sequence), read by the group chain
+        self.noise = [self.torch.empty((t.T, t.n_envs, t.cfg.n_agents, t.cfg.act_dim), dtype=self.torch.float32,
+                                       device=self.device) for t in self.trainers]
+
+    def _sample_group(self):
+        torch = self.torch
+        for t, slab in zip(self.trainers, self.noise):
+            for step in range(t.T):
+                torch.randn(tuple(slab.shape[1:]), generator=t.noise_gen, out=slab[step])
+        self.rollout_group.run(self.noise)
+        for t in self.trainers:
+            t._sample_finish()
+
     def train(self):
         """One iteration of every member; the list of the members' result dicts."""
         t0 = time.perf_counter()
-        for t in self.trainers:
-            t._sample()
+        if self.rollout_group is not None:
+            self._sample_group()
+        else:
+            for t in self.trainers:
+                t._sample()
         self.torch.cuda.synchronize(self.device)
         t1 = time.perf_counter()
         sched = [t._learn_schedules() for t in self.trainers]
@@ -70,6 +109,10 @@ class PopulationTrainer:
             t.restore(os.path.join(directory, f"seed_{s}.npz"))
 
     def stop(self):
+        if getattr(self, "rollout_group", None) is not None:   # before its members and their envs
+            self.rollout_group.close()
+            self.rollout_group = None
+        self.noise = []
         if self.group is not None:   # before its members
             self.group.close()
             self.group = None

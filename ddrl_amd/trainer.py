@@ -200,6 +200,12 @@ class PPOTrainer:
 
     # -- one iteration ---------------------------------------------------------------
     def _sample(self):
+        self._sample_fragment()
+        self._sample_finish()
+
+    def _sample_fragment(self):
+        """The fragment loop: T steps of act / env step / reward / observe, then the bootstrap.
+        (A population replaces its members' loops by one group chain: ddrl_amd.population.)"""
         torch, cfg = self.torch, self.cfg
         rctx = self.rctx
         for t in range(self.T):
@@ -210,6 +216,11 @@ class PPOTrainer:
             rctx.reward(t, fw, cfrc, self.actions, done)
             rctx.observe(obs)
         rctx.bootstrap()
+
+    def _sample_finish(self):
+        """The part after the fragment (this trainer's own, or a group's): advantages, the episode
+        accounting and the cross-rank syncs."""
+        rctx = self.rctx
         rctx.gae()
         self._episode_rows = self._collect_episodes()
         if self.parallel == "gather":

@@ -509,6 +509,36 @@ int ddrl_update_group_plan(int n_members, int n_policies, int max_chains, int32_
 int ddrl_update_group_placement(ddrl_update_group* group, int32_t* xcc, int n_blocks);
 int ddrl_update_group_destroy(ddrl_update_group* group);
 
+/* Group rollout (rollout_group.hip): the device-plane fragments of n_members same-shaped contexts
+ * as ONE in-order chain of launches, the member in the grid's z.  Member m is the context
+ * members[m] with its own device env plane envs[m] (created on that context); every member stays
+ * a full, ordinary context and env, and the chain leaves on each, bit for bit, what
+ * ddrl_rollout_devenv(members[m], envs[m], eps_dev[m], reset) alone leaves: records, last values,
+ * both filters, the env state and the host-side notes, so ddrl_gae, ddrl_episodes_collect and the
+ * update (solo or group) follow on a member unchanged.  fcnet models only.
+ *   create: members[n_members] and envs[n_members], all on one device and one stream (the group
+ *     enqueues on it).  Refuses, naming the member and the reason: no member, a null or repeated
+ *     context or env, a GraphNet member, a ddrl_cfg that differs from member 0's in anything the
+ *     rollout kernels read (n_envs and frag_len included), an env bound to another context than
+ *     its member, another device or stream, members whose terrain on / off or target-velocity
+ *     mode (list draws / per-env table) differ -- the step kernel's instance is one per launch.
+ *     The group owns the member table (device, filled from a pinned host buffer).  Destroy the
+ *     group before its members and their envs.
+ *   run: eps_dev[n_members], each [T][N][n_agents][A] in device memory.  If reset, every member's
+ *     ddrl_devenv_reset and observe first.  Then for t in [0, T): act(t) -> env step -> reward(t)
+ *     -> filter push -> (per-policy filter) -> observe, and the bootstrap: 6 to 8 launches per
+ *     step for the whole group.  The member table is rebuilt from the members' current state at
+ *     every run, so a time limit, target velocities or terrain set between runs hold.  The
+ *     launches are issued directly (no graph); no host synchronization except, from the second
+ *     run on, a wait for the previous run's table copy.  Refuses what create refuses of a
+ *     member's env, stream, terrain and velocity mode, and a null noise buffer; after a refusal
+ *     destroy remains valid. */
+typedef struct ddrl_rollout_group ddrl_rollout_group;
+int ddrl_rollout_group_create(ddrl_ctx* const* members, ddrl_devenv* const* envs, int n_members,
+                              ddrl_rollout_group** out);
+int ddrl_rollout_group_run(ddrl_rollout_group* group, const float* const* eps_dev, int reset);
+int ddrl_rollout_group_destroy(ddrl_rollout_group* group);
+
 /* Data-parallel (shared policy) primitives: gradient of (1/minibatch) * sum over the
  * given rows -> grad_dev[n_params]; after the caller's all-reduce (RCCL), apply clip +
  * Adam.  rows_dev holds n_rows (<= 128) record indices.  stats_step >= 0 also writes this

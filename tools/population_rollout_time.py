@@ -1,0 +1,227 @@
+"""Timing of the group rollout ("Population rollout").
+
+One session, device events around whole calls after a warm-up, three alternating runs of each
+variant per size.  One fragment (T steps and the bootstrap) of M members on the device env plane:
+  group       one RolloutGroup.run (table copy and T x (6 .. 8) + 1 launches for all members);
+  replays     M Context.rollout_devenv calls in stream order (a replayed HIP graph each);
+  python      the per-step Python loop PPOTrainer._sample_fragment runs for each member in turn
+              (its per-step noise draw included, as the trainer issues it);
+  noise       the M x T per-step generator draws into the members' slabs alone -- what a population
+              adds in front of `group` (and a caller of `replays` needs too).
+Sizes: Local at (M, n) = (1, 4096), (16, 4096), (1, 80), (16, 80) and SharedDecentral at (64, 80),
+T = 200.  Per size: milliseconds per call (median, min - max), the ratio replays / group per run,
+and whether the group beat the replays in every run by more than the replays' own spread.
+  --iterations: whole PopulationTrainer.train() iterations (wall clock, sampling and learning apart)
+    at (16, 80) and (16, 4096), group_rollout on and off, alternating.
+  --parent-root DIR (a built checkout of the parent commit): the solo ddrl_rollout_devenv fragment
+    and bench.py's headline on this tree and on the parent's, child processes, alternating.
+Writes one JSON document (default profiles/population/rollout_time.json).
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LOCAL, C4 = "QuantrupedMultiEnv_Local", "QuantrupedMultiEnv_SharedDecentral"
+
+
+def summary(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+
+
+def timed(fn):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)   # ms
+
+
+def make_members(N, make_cfg, env, n_envs, T, M):
+    """M contexts with their own weights and device env plane, reset and observed."""
+    import numpy as np
+    import torch
+    from ddrl_amd.trainer import glorot_ffn_flat
+    cfg, _ = make_cfg(env, n_envs, T)
+    out = []
+    for m in range(M):
+        ctx = N.Context(cfg, 0, torch.cuda.current_stream().cuda_stream)
+        rng = np.random.default_rng(100 + m)
+        for p in range(cfg.n_policies):
+            ctx.params_set(p, glorot_ffn_flat(rng, cfg.obs_dim[p], cfg.act_dim))
+        env_m = N.DevEnv(ctx, seed=7 + m)
+        ctx.observe(env_m.reset())
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(1000 + m)
+        slab = torch.empty((T, n_envs, cfg.n_agents, cfg.act_dim), dtype=torch.float32, device="cuda")
+        actions = torch.zeros((n_envs, 8), dtype=torch.float32, device="cuda")
+        out.append((ctx, env_m, gen, slab, actions))
+    return out, cfg
+
+
+def time_size(N, make_cfg, env, n_envs, T, M, repeats):
+    import torch
+    members, cfg = make_members(N, make_cfg, env, n_envs, T, M)
+    group = N.RolloutGroup([x[0] for x in members], [x[1] for x in members])
+    shape = (n_envs, cfg.n_agents, cfg.act_dim)
+
+    def draws():
+        for ctx, env_m, gen, slab, actions in members:
+            for t in range(T):
+                torch.randn(shape, generator=gen, out=slab[t])
+
+    def run_group():
+        group.run([x[3] for x in members])
+
+    def run_replays():
+        for ctx, env_m, gen, slab, actions in members:
+            ctx.rollout_devenv(env_m, slab)
+
+    def run_python():
+        for ctx, env_m, gen, slab, actions in members:
+            for t in range(T):
+                eps = torch.randn(shape, device="cuda", generator=gen)
+                ctx.act(t, eps, actions)
+                env_m.step(actions)
+                ctx.reward(t, env_m.fw, env_m.cfrc, actions, env_m.done)
+                ctx.observe(env_m.obs)
+            ctx.bootstrap()
+    variants = {"noise": draws, "group": run_group, "replays": run_replays, "python": run_python}
+    for fn in variants.values():   # warm-up: code objects, clocks, the graph captures
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in variants}
+    for _ in range(repeats):
+        for k, fn in variants.items():
+            ms[k].append(timed(fn))
+    group.close()
+    for ctx, env_m, *_ in members:
+        env_m.close()
+        ctx.close()
+    spread = max(ms["replays"]) - min(ms["replays"])
+    res = {"env": env, "members": M, "envs": n_envs, "frag_len": T, "ms": ms,
+           **{f"{k}_ms": summary(v) for k, v in ms.items()},
+           "replays_over_group": [b / a for a, b in zip(ms["group"], ms["replays"])],
+           "python_over_group": [b / a for a, b in zip(ms["group"], ms["python"])],           "group_us_per_step": statistics.median(ms["group"]) * 1e3 / T,
+           "replays_spread_ms": spread,
+           "group_beats_replays_every_run_by_more_than_their_spread":
+               bool(all(b - a > spread for a, b in zip(ms["group"], ms["replays"])))}
+    print(json.dumps({k: v for k, v in res.items() if k != "ms"}), flush=True)
+    return res
+
+
+def time_iterations(M, n_envs, T, repeats):
+    """Whole PopulationTrainer.train() iterations, group_rollout on and off, alternating."""
+    from ddrl_amd.population import PopulationTrainer
+    config = {"env": LOCAL, "env_backend": "device", "rollout_fragment_length": T}
+    pops = {name: PopulationTrainer(config, range(M), n_envs=n_envs, group_rollout=on)
+            for name, on in (("group_rollout", True), ("member_sampling", False))}
+    out = {name: {"iteration_ms": [], "sample_ms": [], "learn_ms": []} for name in pops}
+    for it in range(repeats + 1):   # the first iteration of each is the warm-up
+        for name, pop in pops.items():
+            t0 = time.perf_counter()
+            r = pop.train()
+            dt = (time.perf_counter() - t0) * 1e3
+            if it:
+                out[name]["iteration_ms"].append(dt)
+                out[name]["sample_ms"].append(r[0]["timers"]["sample_time_ms"])
+                out[name]["learn_ms"].append(r[0]["timers"]["learn_time_ms"])
+    for pop in pops.values():
+        pop.stop()
+    res = {"members": M, "envs": n_envs, "frag_len": T,
+           **{name: {k: summary(v) for k, v in d.items()} for name, d in out.items()}}
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def solo_child(root, n_envs, T, repeats):
+    """Child process: the solo ddrl_rollout_devenv fragment of Local on the tree at `root`; one JSON line."""
+    sys.path.insert(0, root)
+    import torch
+    from ddrl_amd import native as N
+    from ddrl_amd.spec import make_cfg
+    members, cfg = make_members(N, make_cfg, LOCAL, n_envs, T, 1)
+    ctx, env_m, gen, slab, actions = members[0]
+    slab.normal_(generator=gen)
+    run = lambda: ctx.rollout_devenv(env_m, slab)
+    run()
+    torch.cuda.synchronize()
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "ms": [timed(run) for _ in range(repeats)]}))
+
+
+def child_json(cmd, cwd, what):
+    r = subprocess.run(cmd, cwd=cwd, capture_output=True, text=True, timeout=900)
+    if r.returncode != 0:
+        sys.exit(f"population_rollout_time: {what} failed:\n{r.stderr[-2000:]}")
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def against(out, unit):
+    res = {"unit": unit, "this": summary(out["this"]), "parent": summary(out["parent"]), "runs": out}
+    res["parent_spread"] = res["parent"]["max"] - res["parent"]["min"]
+    res["this_minus_parent"] = res["this"]["median"] - res["parent"]["median"]
+    res["within_parent_spread"] = bool(abs(res["this_minus_parent"]) <= res["parent_spread"])
+    print(json.dumps({k: v for k, v in res.items() if k != "runs"}), flush=True)
+    return res
+
+
+def solo_regression(a):
+    trees = (("this", HERE), ("parent", os.path.abspath(a.parent_root)))
+    frag = {"this": [], "parent": []}
+    bench = {"this": [], "parent": []}
+    for rnd in range(a.rounds):
+        for name, root in (trees if rnd % 2 == 0 else trees[::-1]):   # neither tree always follows the other
+            frag[name] += child_json([sys.executable, os.path.abspath(__file__), "--solo-child", root, "--envs", str(a.envs),
+                                      "--frag-len", str(a.frag_len), "--repeats", str(a.repeats)], root,
+                                     f"the solo child of {root}")["ms"]
+            bench[name].append(child_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+                                           "--warmup", "1"], root, f"bench.py of {root}")["value"])
+    return {"fragment": against(frag, f"milliseconds per solo ddrl_rollout_devenv fragment, Local, {a.envs} envs x "
+                                      f"{a.frag_len} steps; {a.rounds} alternating processes per tree x {a.repeats}"),
+            "bench": against(bench, f"bench.py --gpus 1 --steps 3 --warmup 1 headline (env-steps/s); {a.rounds} "
+                                    "alternating processes per tree")}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096, help="the large size (the small one is 80)")
+    ap.add_argument("--frag-len", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=2, help="--parent-root: processes per tree")
+    ap.add_argument("--sizes", default="local:1:4096,local:16:4096,local:1:80,local:16:80,c4:64:80",
+                    help="env:members:envs, comma separated ('' skips the fragment timing)")
+    ap.add_argument("--iterations", default="16:80,16:4096", help="members:envs of the whole-iteration timing ('' skips it)")
+    ap.add_argument("--parent-root", default="", help="a built checkout of the parent commit (the solo regression)")
+    ap.add_argument("--solo-child", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--commit", default="")
+    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "population", "rollout_time.json"))
+    a = ap.parse_args()
+    if a.solo_child:
+        return solo_child(a.solo_child, a.envs, a.frag_len, a.repeats)
+    sys.path.insert(0, HERE)
+    import torch
+    from ddrl_amd import native as N
+    from ddrl_amd.spec import make_cfg
+    if not torch.cuda.is_available():
+        sys.exit("population_rollout_time: needs a GPU (no timing without one)")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "commit": a.commit, "frag_len": a.frag_len, "repeats": a.repeats}
+    if a.parent_root:
+        res["solo"] = solo_regression(a)
+    envs = {"local": LOCAL, "c4": C4}
+    res["fragment"] = [time_size(N, make_cfg, envs[e], int(n), a.frag_len, int(m), a.repeats)
+                       for e, m, n in (s.split(":") for s in a.sizes.split(",") if s)]
+    res["iterations"] = [time_iterations(int(m), int(n), a.frag_len, a.repeats)
+                         for m, n in (s.split(":") for s in a.iterations.split(",") if s)]
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
