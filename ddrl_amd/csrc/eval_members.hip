@@ -92,19 +92,18 @@ void launch_eval_act_members(hipStream_t s, const RouteArgs& ra, const EvalMembe
 
 // ------------------------------------------------------------------------------------
 // Env-side MeanStdFilter push of every member: k_filter_chunk / k_filter_merge (rollout.hip) with
-// the member in the grid.  Chunks of FPM_ROWS rows are counted from the member's first env and
+// the member in the grid.  Chunks of FP_ROWS rows are counted from the member's first env and
 // merged in order with the same expressions.  The merge kernel also advances the member's counts
 // (the plain path leaves that to the kernel behind it): its 64 lanes read the counts, meet a
 // barrier, and lane 0 writes them.
 // ------------------------------------------------------------------------------------
-#define FPM_ROWS 256   // rows per chunk, rollout.hip's FP_ROWS
 __global__ void __launch_bounds__(256) k_filter_chunk_members(const float* __restrict__ obs, int N, int D,
                                                               double* __restrict__ part, size_t part_stride) {
   const int j = blockIdx.x, sc = blockIdx.y, m = blockIdx.z;
   __shared__ double red[4];
   const int tid = threadIdx.x, w = tid >> 6;
-  const int e = sc * FPM_ROWS + tid;   // within the member
-  const int n_c = min(FPM_ROWS, N - sc * FPM_ROWS);
+  const int e = sc * FP_ROWS + tid;   // within the member
+  const int n_c = min(FP_ROWS, N - sc * FP_ROWS);
   const float x = e < N ? obs[((size_t)m * N + e) * D + j] : 0.f;
   double acc = wave_sum_d((double)x);
   if ((tid & 63) == 0) red[w] = acc;
@@ -133,11 +132,11 @@ __global__ void __launch_bounds__(64) k_filter_merge_members(int N, int D, const
     double Mj = F[FM_M + j], Sj = F[FM_S + j];
     if (push) {
       // the batch's (mean, M2): the chunks merged in order (Chan et al.)
-      const int nchunks = (N + FPM_ROWS - 1) / FPM_ROWS;
+      const int nchunks = (N + FP_ROWS - 1) / FP_ROWS;
       double nb = 0.0, mean_b = 0.0, s_b = 0.0;
       for (int c = 0; c < nchunks; ++c) {
         const double* pc = pm + ((size_t)c * D + j) * 2;
-        const double nc = (double)min(FPM_ROWS, N - c * FPM_ROWS), nn = nb + nc, d = pc[0] - mean_b;
+        const double nc = (double)min(FP_ROWS, N - c * FP_ROWS), nn = nb + nc, d = pc[0] - mean_b;
         mean_b = (nb * mean_b + nc * pc[0]) / nn;
         s_b = s_b + pc[1] + d * d * nb * nc / nn;
         nb = nn;
@@ -170,7 +169,7 @@ void launch_filter_push_members(hipStream_t s, const float* obs, int n, int D, i
   const int push = enabled && update;
   const size_t part_stride = filter_part_doubles(n, D);
   if (push)
-    hipLaunchKernelGGL(k_filter_chunk_members, dim3(D, (n + FPM_ROWS - 1) / FPM_ROWS, n_members), dim3(256), 0, s, obs,
+    hipLaunchKernelGGL(k_filter_chunk_members, dim3(D, (n + FP_ROWS - 1) / FP_ROWS, n_members), dim3(256), 0, s, obs,
                        n, D, part, part_stride);
   hipLaunchKernelGGL(k_filter_merge_members, dim3(n_members), dim3(64), 0, s, n, D, part, part_stride, filt, push,
                      enabled);

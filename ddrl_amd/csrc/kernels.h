@@ -51,6 +51,7 @@ inline RowGeom row_geom(const RouteArgs& ra, int n_envs) {
 // ---- filter / observe (rollout.hip) ----
 // dn / dM / dS: a second running stat of the pushes since the last cross-rank filter sync
 // part: filter_part_doubles(N, D) doubles of per-chunk (mean, M2) scratch
+#define FP_ROWS 256   // rows per filter chunk: one per thread
 void launch_filter_push(hipStream_t s, const float* obs, int N, int D, double* n_run, double* M,
                         double* S, double* normc, int update, int enabled, double* dn, double* dM,
                         double* dS, double* part);

@@ -1,5 +1,6 @@
-// The row pipeline around the fcnet forward, shared by the rollout kernels (rollout.hip), the
-// fused evaluation forward (eval.hip) and the input-sensitivity kernel (eval_sens.hip): the
+// The row pipeline around the fcnet forward, shared by the rollout kernels (rollout.hip and, through
+// the same body texts, rollout_group.hip), the fused evaluation forward (eval.hip, eval_members.hip)
+// and the input-sensitivity kernel (eval_sens.hip): the
 // observation arithmetic (env-side normalization, routing, per-policy filter), the action
 // epilogue (clip, sign flip, scatter) and the per-agent reward.  One body each,
 // so the kernels agree bit for bit by construction; every function is force-inlined into its
@@ -32,6 +33,13 @@ __device__ __forceinline__ double norm_obs_d(float x, const double* normc, int i
 }
 __device__ __forceinline__ float norm_obs(float x, const double* normc, int idx, float clip) {
   return (float)norm_obs_d(x, normc, idx, clip);
+}
+
+// RunningStat.update (Chan et al.): the batch (nb, mb, sb) merged into the running (n, M, S), n left to the caller
+__device__ __forceinline__ void chan_merge(double& n, double& M, double& S, double nb, double mb, double sb) {
+  const double tot = n + nb, delta = M - mb;
+  M = (n * M + nb * mb) / tot;
+  S = S + sb + delta * delta * n * nb / tot;
 }
 
 // the normalization constants (mean, std + 1e-8 per column) of policy p's filter; null: no filter

@@ -6,6 +6,11 @@
 // :124-136 (distribute_observations), :160-212 (contact cost, rewards, concatenate_actions);
 // models/fcnet_glorot_uniform_init.py:120-125 (forward / value_function);
 // RLlib DiagGaussian sampling with clip_actions=True.
+//
+// The bodies of the kernels of a device-plane training step (filter chunk / merge, zstats / pfilter,
+// observe, act, reward) are texts of their own (*_body.h), included inside the kernel's braces here and
+// in rollout_group.hip's member-axis kernels: the signature names the operands, an accessor macro the
+// fields of a by-value argument block the text reads (defined here, undefined at the text's end).
 #include "common.h"
 #include "kernels.h"
 #include "ffn.h"
@@ -22,64 +27,15 @@
 // 4096 envs.  The same chunks merged by the last-arriving workgroup of a column -- agent-scope
 // acq_rel atomics, one L2 write-back per workgroup -- measured 18.3 us.)
 // ------------------------------------------------------------------------------------
-#define FP_ROWS 256   // rows per chunk: one per thread
 __global__ void __launch_bounds__(256) k_filter_chunk(const float* __restrict__ obs, int N, int D,
                                                       double* __restrict__ part) {
-  const int j = blockIdx.x, sc = blockIdx.y;
-  __shared__ double red[4];
-  const int tid = threadIdx.x, w = tid >> 6;
-  const int e = sc * FP_ROWS + tid;
-  const int n_c = min(FP_ROWS, N - sc * FP_ROWS);
-  const float x = e < N ? obs[(size_t)e * D + j] : 0.f;
-  double acc = wave_sum_d((double)x);
-  if ((tid & 63) == 0) red[w] = acc;
-  __syncthreads();
-  const double mean_c = ((red[0] + red[1]) + (red[2] + red[3])) / (double)n_c;
-  __syncthreads();
-  const double dlt = e < N ? (double)x - mean_c : 0.0;
-  acc = wave_sum_d(dlt * dlt);
-  if ((tid & 63) == 0) red[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double* pc = part + ((size_t)sc * D + j) * 2;
-    pc[0] = mean_c;
-    pc[1] = (red[0] + red[1]) + (red[2] + red[3]);
-  }
+#include "filter_chunk_body.h"
 }
 
 __global__ void k_filter_merge(int N, int D, const double* __restrict__ part, double* n_run, double* M,
                                double* S, double* normc, int push, int enabled, double* dn, double* dM,
                                double* dS) {
-  const int j = threadIdx.x;
-  if (j >= D) return;
-  double n1 = n_run[0];
-  double Mj = M[j], Sj = S[j];
-  if (push) {
-    // the batch's (mean, M2): the chunks merged in order (Chan et al.)
-    const int nchunks = (N + FP_ROWS - 1) / FP_ROWS;
-    double nb = 0.0, mean_b = 0.0, s_b = 0.0;
-    for (int c = 0; c < nchunks; ++c) {
-      const double* pc = part + ((size_t)c * D + j) * 2;
-      const double nc = (double)min(FP_ROWS, N - c * FP_ROWS), nn = nb + nc, d = pc[0] - mean_b;
-      mean_b = (nb * mean_b + nc * pc[0]) / nn;
-      s_b = s_b + pc[1] + d * d * nb * nc / nn;
-      nb = nn;
-    }
-    const double n2 = (double)N, n = n1 + n2;
-    const double delta = Mj - mean_b;
-    Mj = (n1 * Mj + n2 * mean_b) / n;
-    Sj = Sj + s_b + delta * delta * n1 * n2 / n;
-    n1 = n;
-    M[j] = Mj;
-    S[j] = Sj;
-    // the same batch merged into the delta buffer (pushes since the last filter sync)
-    const double d1 = dn[0], dd = d1 + n2, ddl = dM[j] - mean_b;
-    dM[j] = (d1 * dM[j] + n2 * mean_b) / dd;
-    dS[j] = dS[j] + s_b + ddl * ddl * d1 * n2 / dd;
-  }
-  const double var = n1 > 1.0 ? Sj / (n1 - 1.0) : Mj * Mj;
-  normc[2 * j] = enabled ? Mj : 0.0;
-  normc[2 * j + 1] = enabled ? sqrt(var) + 1e-8 : 1.0;
+#include "filter_merge_body.h"
 }
 
 size_t filter_part_doubles(int N, int D) { return (size_t)2 * D * ((N + FP_ROWS - 1) / FP_ROWS); }
@@ -99,16 +55,8 @@ __global__ void k_observe_ffn(RouteArgs ra, const float* __restrict__ obs,
                               const double* __restrict__ normc, float clip, float* const* stage_tab,
                               const double* __restrict__ pf, FilterCount fc) {
   filter_count(fc);
-  const int p = blockIdx.y;
-  const PolicyRoute& pr = ra.pol[p];
-  const int C = ra.N * pr.k;              // rows of the env range [e0, e0 + N)
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= C * pr.d) return;
-  const int cl = gid / pr.d, f = gid - cl * pr.d;
-  const int el = cl / pr.k, slot = cl - el * pr.k;
-  const int e = ra.e0 + el, c = ra.e0 * pr.k + cl;
-  stage_tab[p][(size_t)c * pr.d + f] =
-      routed_input(pr, slot, f, obs + (size_t)e * ra.full_dim, normc, clip, policy_filter_normc(pf, p));
+#define OBSERVE_E0 ra.e0
+#include "observe_ffn_body.h"
 }
 
 void launch_observe_ffn(hipStream_t s, const RouteArgs& ra, const float* obs, const double* normc,
@@ -129,65 +77,11 @@ void launch_observe_ffn(hipStream_t s, const RouteArgs& ra, const float* obs, co
 __global__ void __launch_bounds__(256) k_zstats(const float* __restrict__ obs, int N, int D,
                                                 const double* __restrict__ normc, float clip,
                                                 double* __restrict__ zs) {
-  const int j = blockIdx.x, tid = threadIdx.x;
-  __shared__ double red[2][4];
-  double s1 = 0.0, s2 = 0.0;
-  for (int e = tid; e < N; e += 256) {
-    const double z = norm_obs_d(obs[(size_t)e * D + j], normc, j, clip);
-    s1 += z;
-    s2 += z * z;
-  }
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
-  if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
-  __syncthreads();
-  if (tid == 0) {
-    zs[2 * j] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    zs[2 * j + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
-}
-
-__device__ __forceinline__ void chan_merge(double& n, double& M, double& S, double nb, double mb, double sb) {
-  const double tot = n + nb, delta = M - mb;
-  M = (n * M + nb * mb) / tot;
-  S = S + sb + delta * delta * n * nb / tot;
+#include "zstats_body.h"
 }
 
 __global__ void k_pfilter(RouteArgs ra, const double* __restrict__ zs, double* pf, int update) {
-  const int p = blockIdx.x, f = threadIdx.x;
-  const PolicyRoute& pr = ra.pol[p];
-  double* P = pf + (size_t)p * PF_STRIDE;
-  const double n0 = P[PF_N], dn0 = P[PF_DN];
-  const double nb = (double)ra.N * pr.k;
-  __syncthreads();
-  if (f < pr.d) {
-    double M = P[PF_M + f], S = P[PF_S + f], n = n0;
-    if (update) {
-      double s1 = 0.0, s2 = 0.0;
-      for (int s = 0; s < pr.k; ++s) {
-        const int idx = pr.obs_index[s][f];
-        s1 += zs[2 * idx];
-        s2 += zs[2 * idx + 1];
-      }
-      const double mb = s1 / nb, sb = fmax(s2 - s1 * mb, 0.0);
-      chan_merge(n, M, S, nb, mb, sb);
-      double dn = dn0, dM = P[PF_DM + f], dS = P[PF_DS + f];
-      chan_merge(dn, dM, dS, nb, mb, sb);
-      P[PF_M + f] = M;
-      P[PF_S + f] = S;
-      P[PF_DM + f] = dM;
-      P[PF_DS + f] = dS;
-      n = n0 + nb;
-    }
-    const double var = n > 1.0 ? S / (n - 1.0) : M * M;
-    P[PF_NORMC + 2 * f] = M;
-    P[PF_NORMC + 2 * f + 1] = sqrt(var) + 1e-8;
-  }
-  __syncthreads();
-  if (update && f == 0) {
-    P[PF_N] = n0 + nb;
-    P[PF_DN] = dn0 + nb;
-  }
+#include "pfilter_body.h"
 }
 
 void launch_policy_filter(hipStream_t s, const RouteArgs& ra, const float* obs, const double* normc, float clip,
@@ -237,82 +131,8 @@ void launch_observe_gnn(hipStream_t s, const RouteArgs& ra, const float* obs, co
 // ------------------------------------------------------------------------------------
 template <int A, int KS1>
 __global__ void __launch_bounds__(512) k_act_ffn(RouteArgs ra, ActArgs aa) {
-  constexpr int O = 2 * A;
-  extern __shared__ float lds[];
-  const int p = blockIdx.y;
-  const PolicyRoute& pr = ra.pol[p];
-  const int C = aa.C[p];
-  const int row_hi = aa.e1 * pr.k;        // rows of the env range [e0, e1)
-  const int row0 = aa.e0 * pr.k + blockIdx.x * 64;
-  if (row0 >= row_hi) return;
-  const int d = pr.d;
-  NetLds PW, VW;
-  stage_weights(aa.theta[p], d, A, lds, PW, VW, 512);
-  __syncthreads();
-
-  const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4, w = threadIdx.x >> 6;
-  const bool value_wave = w >= 4;
-  if (aa.bootstrap && !value_wave) return;   // bootstrap: V(s_T) only
-  const int row = row0 + 16 * (w & 3) + c;
-  const bool valid = row < row_hi;
-  const float* xs = aa.stage[p] + (size_t)(valid ? row : 0) * d;
-  float xop[12];
-#pragma unroll
-  for (int s = 0; s < 12; ++s) {
-    const int f = 4 * s + q;
-    xop[s] = (s < KS1 && f < d && valid) ? xs[f] : 0.f;
-  }
-  floatx4 h1[4], h2[4];
-  const RecLayout& L = aa.lay[p];
-  if (value_wave) {
-    float vout[1];
-    ffn_branch_fwd<1, KS1>(VW, xop, h1, h2, vout);
-    if (valid && q == 0) {
-      if (aa.bootstrap) aa.last_v[p][row] = vout[0];
-      else aa.rec[p][((size_t)aa.t * C + row) * L.stride + L.vf] = vout[0];
-    }
-    return;
-  }
-  float logits[O];
-  ffn_branch_fwd<O, KS1>(PW, xop, h1, h2, logits);
-  if (!valid) return;
-  float* rp = aa.rec[p] + ((size_t)aa.t * C + row) * L.stride;
-  const int e = row / pr.k, slot = row - e * pr.k;
-  const int agent = pr.agent[slot];
-  // "cup" model (coupling_net_glorot_uniform_init.py:22-30): mean_j *= coupling[leg][j], the
-  // log-std half is padded with ones; leg = the agent's index in the env (one shared policy)
-  if (aa.cup[p]) {
-#pragma unroll
-    for (int j = 0; j < A; ++j) logits[j] *= aa.cup[p][slot * A + j];
-  }
-  // sample + logp (DiagGaussian, RLlib 1.0): a = mean + std * eps
-  float logp = -0.5f * (float)(DDRL_LOG2PI * A);
-  float act[A];
-#pragma unroll
-  for (int j = 0; j < A; ++j) {
-    const float mu = logits[j], ls = logits[A + j];
-    const float sd = expf(ls);
-    const float eps = aa.eps[((size_t)e * ra.n_agents + agent) * A + j];
-    act[j] = mu + sd * eps;
-    const float z = (act[j] - mu) / sd;
-    logp -= 0.5f * z * z;
-    logp -= ls;
-  }
-  // q-lanes split the record stores
-  for (int f = q; f < d; f += 4) rp[L.obs + f] = xs[f];
-  if (q == 0) {
-#pragma unroll
-    for (int j = 0; j < A; ++j) {
-      rp[L.act + j] = act[j];
-      scatter_action(aa.actions, pr, e, slot, j, act[j]);
-    }
-  } else if (q == 1) {
-#pragma unroll
-    for (int j = 0; j < O; ++j) rp[L.logit + j] = logits[j];
-  } else if (q == 2) {
-    rp[L.logp] = logp;
-    if (L.cid >= 0) rp[L.cid] = (float)slot;
-  }
+#define ACT(field) aa.field
+#include "act_ffn_body.h"
 }
 
 template <int A, int KS1>
@@ -333,16 +153,9 @@ void launch_act_ffn(hipStream_t s, const RouteArgs& ra, const ActArgs& aa) {
 __global__ void k_reward(RewardArgs ra, const float* __restrict__ fw, const float* __restrict__ cfrc,
                          const float* __restrict__ actions, const uint8_t* __restrict__ done,
                          uint8_t* __restrict__ done_tn) {
-  const int na = ra.n_agents;
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= ra.n * na) return;
-  const int el = gid / na, j = gid - el * na, e = ra.e0 + el;
-  const double r = agent_reward_d(ra, j, (double)fw[e], cfrc + (size_t)e * 14 * 6, actions + (size_t)e * 8);
-  const int p = ra.policy_of_agent[j], slot = ra.slot_of_agent[j];
-  const size_t C = (size_t)ra.N * ra.k[p];
-  float* rp = ra.rec[p] + ((size_t)ra.t * C + (size_t)e * ra.k[p] + slot) * ra.lay[p].stride;
-  rp[ra.lay[p].rew] = (float)r;
-  if (j == 0) done_tn[(size_t)ra.t * ra.N + e] = done ? done[e] : 0;
+#define REWARD(field) ra.field
+#define REWARD_DONE(e) (done ? done[e] : 0)   // done is optional: null records no episode ends
+#include "reward_body.h"
 }
 
 void launch_reward(hipStream_t s, const RewardArgs& ra, const float* fw, const float* cfrc,

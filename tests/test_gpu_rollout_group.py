@@ -54,7 +54,8 @@ class Member:
     twin.  The recipe ends with a plain warm-up fragment from a reset, so the state the compared
     fragment starts from is mid-episode: filters pushed, stages filled, envs apart."""
 
-    def __init__(self, env_name, config, n, T, m, limit=1000, tvs=None, smooth=None, warm=True, gnn=False):
+    def __init__(self, env_name, config, n, T, m, limit=1000, tvs=None, smooth=None, warm=True, gnn=False,
+                 tv_env=False):
         self.ctx, self.cfg, _ = make_ctx(env_name, n, T, config)
         ctx, cfg = self.ctx, self.cfg
         if gnn:
@@ -72,6 +73,10 @@ class Member:
                 ctx.policy_filter_set(p, 50.0 + m, rng.normal(size=d) * 0.1, np.abs(rng.normal(size=d)) * 40.0 + 20.0)
         self.env = N.DevEnv(ctx, seed=77 + 13 * m, target_velocity=[v + 0.25 * m for v in tvs] if tvs else 0.0)
         self.env.set_time_limit(limit + m)
+        self.tv_table = None
+        if tv_env:   # a fixed velocity per env, the member's own table; no entry is in the member's list
+            self.tv_table = (1.0 + 0.25 * m + 0.01 * (np.arange(n) + 1)).astype(np.float32)
+            self.env.set_env_target_velocities(self.tv_table)
         if smooth is not None:   # member 0 at `smooth`, the others over a range below it, each its own generation
             self.env.set_terrain(smooth - 0.05 * m, smooth, generation=3 + m)
         else:
@@ -173,6 +178,8 @@ def run_case(env_name, config, M, n, T, runs=1, reset=False, between=None, **kw)
             ga, gb = a.after_gae(), b.after_gae()
             assert_same(ga, gb, f"run {run} member {m} after gae and episodes_collect")
             dones.append((run, m, ga["episodes"]))
+            if a.tv_table is not None:   # the restarts read the table and drew nothing from the list
+                np.testing.assert_array_equal(a.env.target_velocities, a.tv_table, err_msg=f"run {run} member {m}")
         if M > 1:
             assert_members_differ(members)
     group.close()
@@ -217,6 +224,19 @@ def test_episode_ends_inside_the_fragment():
         # the episode rows are {t, env, ...} of every done flag the fragment recorded
         assert set(rows[:, 1].astype(int)) == set(range(n)), (m, rows[:, 1])   # every env of every member ended
         assert n <= len(rows) < n * T, (m, len(rows))                          # ... and not at every step
+
+
+@pytest.mark.parametrize("smooth", [None, 0.8], ids=["flat", "uneven"])
+def test_per_env_target_velocities(smooth):
+    """set_env_target_velocities on every member, each its own table: the per-env-velocity instances
+    of the step kernel, flat and uneven.  n = 70 is two env-step blocks, so the table is read past
+    env 63; TimeLimit 3 (+ m) with T = 8 restarts every env, which then holds its table entry."""
+    n, T, M = 70, 8, 3
+    config = {"env_config": {"target_velocity": TVS}}
+    dones = run_case("QuantrupedMultiEnv_FullyDecentral", config, M, n, T, limit=3, tvs=TVS, smooth=smooth, tv_env=True)
+    assert len(dones) == M
+    for run, m, rows in dones:
+        assert set(rows[:, 1].astype(int)) == set(range(n)), (m, rows[:, 1])   # every env of every member ended
 
 
 def test_uneven_ground():
