@@ -1176,7 +1176,7 @@ static int eval_act_members(ddrl_ctx* c, const float* obs, const float* eps, flo
   RouteArgs ra = c->route;
   ra.e0 = 0;
   ra.N = n;
-  launch_eval_act_members(c->stream, ra, ma, M);
+  launch_eval_act_members(c->stream, ra, ma, M, push ? n : 0);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2302,6 +2302,71 @@ int ddrl_device_buffers(ddrl_ctx* c, int pid, void** records, void** last_v, voi
 
 }  // extern "C"
 
+// ---- what the two groups of contexts (update, rollout) share; `kind` is "update" or "rollout" ----
+namespace {
+// A group's device table of per-member kernel arguments, rebuilt at every run in a pinned host array and copied on
+// the group's stream.  That array is the source of the copy: host() waits for `copied`, recorded behind the copy.
+template <class T>
+struct MemberTable {
+  T *pinned = nullptr, *dev = nullptr;
+  hipEvent_t copied = nullptr;
+  int copy_pending = 0;
+  bool alloc(size_t n) {
+    const size_t bytes = n * sizeof(T);
+    return hipHostMalloc((void**)&pinned, bytes, hipHostMallocDefault) == hipSuccess && hipMalloc((void**)&dev, bytes) == hipSuccess &&
+           hipMemset(dev, 0, bytes) == hipSuccess && hipEventCreateWithFlags(&copied, hipEventDisableTiming) == hipSuccess;
+  }
+  int host(T*& out) {
+    if (copy_pending) HIPCHK(hipEventSynchronize(copied));
+    copy_pending = 0;
+    out = pinned;
+    return 0;
+  }
+  int upload(hipStream_t stream, size_t n) {
+    HIPCHK(hipMemcpyAsync(dev, pinned, n * sizeof(T), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(copied, stream));
+    copy_pending = 1;
+    return 0;
+  }
+  void stream_synced() { copy_pending = 0; }   // the caller has synchronized the stream of the last upload
+  void release() {
+    if (copied) (void)hipEventDestroy(copied);
+    if (pinned) (void)hipHostFree(pinned);
+    if (dev) (void)hipFree(dev);
+  }
+};
+
+std::string group_member_name(const char* kind, int m) { return std::string(kind) + " group: member " + std::to_string(m); }
+
+// create: no null and no repeated member (nor device env, where the group has them: envs != nullptr)
+int group_list_ok(const char* kind, ddrl_ctx* const* members, ddrl_devenv* const* envs, int n_members) {
+  for (int m = 0; m < n_members; ++m) {
+    const std::string name = group_member_name(kind, m);
+    if (!members[m]) return fail(name + " is a null context");
+    if (envs && !envs[m]) return fail(name + " has a null device env");
+    for (int k = 0; k < m; ++k) {
+      if (members[k] == members[m]) return fail(name + " repeats member " + std::to_string(k));
+      if (envs && envs[k] == envs[m]) return fail(name + " repeats the device env of member " + std::to_string(k));
+    }
+  }
+  return 0;
+}
+
+// create: member m is an fcnet context on the group's device
+int group_member_kind(const char* kind, const ddrl_ctx* c, int device, int m) {
+  if (c->device != device) return fail(group_member_name(kind, m) + " is on another device than member 0");
+  if (c->cfg.model_kind != DDRL_MODEL_FFN)
+    return fail(group_member_name(kind, m) + " is a GraphNet context: the group " + kind + " runs the fcnet kernels only");
+  return 0;
+}
+
+// same-shape checks: `why` names the first difference from member 0, found field by field (x.f against y.f)
+#define DDRL_GRP_SAME(f) if (!why && !(x.f == y.f)) why = #f
+int group_same_result(const char* kind, int m, const char* why) {
+  return why ? fail(group_member_name(kind, m) + " differs from member 0 in " + why + ": a group takes contexts of one shape") : 0;
+}
+}  // namespace
+
 // ---- group update (ppo_ffn_group.hip): the fused updates of M same-shaped contexts in one launch ----
 // Chain g = m * P + p is policy p of member m.  The launches of a run hold whole members, in member
 // order; launch l covers the chains [g0_l, g0_l + n_l) of the table and records its blocks' XCC ids
@@ -2311,14 +2376,11 @@ struct ddrl_update_group {
   std::vector<ddrl_ctx*> members;
   int device = 0;
   hipStream_t stream = nullptr;
+  MemberTable<UpdateArgs> table;       // one entry per chain
   int P = 0, cap = 0;                  // policies per member, chains per launch
   std::vector<int32_t> launch_of_member, first_block;
   std::vector<int> launch_g0, launch_n, launch_x0;   // first chain, chains and first xcc slot of each launch
   int xcc_total = 0;
-  UpdateArgs* table_host = nullptr;    // pinned; rewritten only after `copied` (recorded behind its H2D copy)
-  UpdateArgs* table_dev = nullptr;
-  hipEvent_t copied = nullptr;
-  int copy_pending = 0;
   unsigned long long *xchg = nullptr, *gx = nullptr;
   int *err = nullptr, *xcc = nullptr;
   std::vector<int> xcc_host;           // the record of the last finished run
@@ -2345,7 +2407,7 @@ int group_plan(int M, int P, int max_chains, int32_t* launch_of_member, int32_t*
   return 0;
 }
 
-std::string member_name(int m) { return "update group: member " + std::to_string(m); }
+std::string member_name(int m) { return group_member_name("update", m); }
 
 // what a member must still be at every run (create checks it too): the group's stream, the default
 // exchange protocol, no peer
@@ -2363,13 +2425,11 @@ int group_member_ok(const ddrl_update_group* g, int m) {
 int group_same_shape(const ddrl_ctx* a, const ddrl_ctx* b, int m) {
   const ddrl_cfg &x = a->cfg, &y = b->cfg;
   const char* why = nullptr;
-#define DDRL_GRP_SAME(f) if (!why && !(x.f == y.f)) why = #f
   DDRL_GRP_SAME(model_kind); DDRL_GRP_SAME(n_policies); DDRL_GRP_SAME(act_dim); DDRL_GRP_SAME(leg_coupling);
   DDRL_GRP_SAME(sgd_minibatch_size); DDRL_GRP_SAME(num_sgd_iter); DDRL_GRP_SAME(clip_param);
   DDRL_GRP_SAME(vf_clip_param); DDRL_GRP_SAME(vf_loss_coeff); DDRL_GRP_SAME(entropy_coeff); DDRL_GRP_SAME(lr);
   DDRL_GRP_SAME(grad_clip); DDRL_GRP_SAME(adam_beta1); DDRL_GRP_SAME(adam_beta2); DDRL_GRP_SAME(adam_eps);
   DDRL_GRP_SAME(vf_clip_mode);
-#undef DDRL_GRP_SAME
   for (int p = 0; p < x.n_policies && !why; ++p) {
     const Policy &P = a->pol[p], &Q = b->pol[p];
     if (P.d != Q.d) why = "obs_dim";
@@ -2377,14 +2437,12 @@ int group_same_shape(const ddrl_ctx* a, const ddrl_ctx* b, int m) {
     else if (P.R != Q.R || P.nb != Q.nb) why = "frag_len x n_envs (rows per policy)";
     else if (P.n_params != Q.n_params) why = "the parameter count";
   }
-  if (why) return fail(member_name(m) + " differs from member 0 in " + why + ": a group takes contexts of one shape");
-  return 0;
+  return group_same_result("update", m, why);
 }
 
 void group_free(ddrl_update_group* g) {
-  if (g->copied) (void)hipEventDestroy(g->copied);
-  if (g->table_host) (void)hipHostFree(g->table_host);
-  for (void* p : {(void*)g->table_dev, (void*)g->xchg, (void*)g->gx, (void*)g->err, (void*)g->xcc})
+  g->table.release();
+  for (void* p : {(void*)g->xchg, (void*)g->gx, (void*)g->err, (void*)g->xcc})
     if (p) (void)hipFree(p);
   delete g;
 }
@@ -2402,11 +2460,7 @@ int ddrl_update_group_create(ddrl_ctx* const* members, int n_members, int max_ch
   if (!members || !out) return fail("null argument");
   if (n_members < 1) return fail("update group: at least one member is needed");
   if (max_chains_per_launch < 0) return fail("update group: max_chains_per_launch must be >= 0 (0: the device's cap)");
-  for (int m = 0; m < n_members; ++m) {
-    if (!members[m]) return fail(member_name(m) + " is a null context");
-    for (int k = 0; k < m; ++k)
-      if (members[k] == members[m]) return fail(member_name(m) + " repeats member " + std::to_string(k));
-  }
+  if (group_list_ok("update", members, nullptr, n_members)) return -1;
   ddrl_ctx* c0 = members[0];
   HIPCHK(hipSetDevice(c0->device));
   ddrl_update_group* g = new ddrl_update_group();
@@ -2417,8 +2471,7 @@ int ddrl_update_group_create(ddrl_ctx* const* members, int n_members, int max_ch
   int rc = 0;
   for (int m = 0; m < n_members && !rc; ++m) {
     const ddrl_ctx* c = members[m];
-    if (c->device != g->device) rc = fail(member_name(m) + " is on another device than member 0");
-    else if (c->cfg.model_kind != DDRL_MODEL_FFN) rc = fail(member_name(m) + " is a GraphNet context: the group update runs the fcnet kernels only");
+    if (group_member_kind("update", c, g->device, m)) rc = -1;
     else if (c->cfg.sgd_minibatch_size != 128) rc = fail(member_name(m) + " has sgd_minibatch_size " + std::to_string(c->cfg.sgd_minibatch_size) + ": the group kernel is built for 128-row minibatches only");
     else if (c->update_split != 2) rc = fail(member_name(m) + " was created under DDRL_UPDATE_SPLIT=1: the group kernel is the row split");
     else rc = group_member_ok(g, m) || group_same_shape(c, c0, m);
@@ -2450,11 +2503,9 @@ int ddrl_update_group_create(ddrl_ctx* const* members, int n_members, int max_ch
     auto dev = [&](void** p, size_t bytes) {
       return hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess;
     };
-    if (hipHostMalloc((void**)&g->table_host, nchain * sizeof(UpdateArgs), hipHostMallocDefault) != hipSuccess ||
-        !dev((void**)&g->table_dev, nchain * sizeof(UpdateArgs)) ||
-        !dev((void**)&g->xchg, sizeof(unsigned long long) * 8 * rows8) || !dev((void**)&g->gx, gx_bytes(maxn)) ||
+    if (!g->table.alloc(nchain) || !dev((void**)&g->xchg, sizeof(unsigned long long) * 8 * rows8) || !dev((void**)&g->gx, gx_bytes(maxn)) ||
         !dev((void**)&g->err, sizeof(int)) || !dev((void**)&g->xcc, sizeof(int) * (size_t)g->xcc_total) ||
-        hipEventCreateWithFlags(&g->copied, hipEventDisableTiming) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        hipDeviceSynchronize() != hipSuccess)
       rc = fail("update group: allocation failed (" + std::to_string(gx_bytes(maxn) >> 20) + " MB of outboxes)");
     g->xcc_host.assign(g->xcc_total, -1);
   }
@@ -2488,17 +2539,14 @@ int ddrl_update_group_run(ddrl_update_group* g, const int32_t* const* shuffle, c
     }
   }
   HIPCHK(hipSetDevice(g->device));
-  // the pinned table is the source of the previous run's H2D copy: wait for that copy before rewriting it
-  if (g->copy_pending) {
-    HIPCHK(hipEventSynchronize(g->copied));
-    g->copy_pending = 0;
-  }
+  UpdateArgs* table = nullptr;
+  if (g->table.host(table)) return -1;
   int maxd = 0, maxs = 0, hook = 0;
   for (int m = 0; m < M; ++m) {
     ddrl_ctx* c = g->members[m];
     hook |= c->fail_step >= 0;
     for (int p = 0; p < P; ++p) {
-      UpdateArgs& u = g->table_host[m * P + p];
+      UpdateArgs& u = table[m * P + p];
       u = make_update(c, p, shuffle[m * P + p], perm[m * P + p], kl[m * P + p]);
       u.max_steps = max_steps;
       c->kl_last[p] = kl[m * P + p];
@@ -2508,15 +2556,13 @@ int ddrl_update_group_run(ddrl_update_group* g, const int32_t* const* shuffle, c
     }
     if (snapshot(c, (1 << P) - 1)) return -1;
   }
-  HIPCHK(hipMemcpyAsync(g->table_dev, g->table_host, sizeof(UpdateArgs) * (size_t)M * P, hipMemcpyHostToDevice, g->stream));
-  HIPCHK(hipEventRecord(g->copied, g->stream));
-  g->copy_pending = 1;
+  if (g->table.upload(g->stream, (size_t)M * P)) return -1;
   // test hook (DDRL_TEST_FAIL_STEP on any member): the run starts with the group's error word set,
   // as launch_ffn does for a context -- every chain runs its steps and none writes back
   if (hook) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)g->err, 1, 1, g->stream));
   const UpdateHyper h = make_hyper(c0, P);
   for (size_t l = 0; l < g->launch_n.size(); ++l)
-    if (launch_update_ffn_group(g->stream, g->table_dev + g->launch_g0[l], g->launch_n[l], h, c0->cfg.act_dim, maxd, maxs,
+    if (launch_update_ffn_group(g->stream, g->table.dev + g->launch_g0[l], g->launch_n[l], h, c0->cfg.act_dim, maxd, maxs,
                                 c0->cfg.leg_coupling, g->xchg, g->gx, g->err, &g->epoch, g->xcc + g->launch_x0[l])) {
       for (ddrl_ctx* c : g->members) c->snap_mask = 0;   // nothing ran: nothing to restore
       (void)hipMemsetAsync(g->err, 0, sizeof(int), g->stream);
@@ -2533,7 +2579,7 @@ int ddrl_update_group_finish(ddrl_update_group* g) {
   HIPCHK(hipSetDevice(g->device));
   HIPCHK(hipStreamSynchronize(g->stream));
   g->inflight = 0;
-  g->copy_pending = 0;
+  g->table.stream_synced();
   HIPCHK(hipGetLastError());
   int e = 0;
   HIPCHK(hipMemcpy(&e, g->err, sizeof(int), hipMemcpyDeviceToHost));
@@ -2593,21 +2639,17 @@ int ddrl_update_group_destroy(ddrl_update_group* g) {
 // Member m is the context members[m] with its own device env plane envs[m].  The kernels read what
 // differs between members from a device table of RolloutMember, rebuilt at every run from the
 // members' current state (so terrain, time limit and target velocities set between runs hold) in
-// a pinned host buffer the group owns, and copied on the stream; `copied` is recorded behind that
-// copy and waited on before the buffer is rewritten.
+// the group's MemberTable.
 struct ddrl_rollout_group {
   std::vector<ddrl_ctx*> members;
   std::vector<ddrl_devenv*> envs;
   int device = 0;
   hipStream_t stream = nullptr;
-  RolloutMember* table_host = nullptr;   // pinned
-  RolloutMember* table_dev = nullptr;
-  hipEvent_t copied = nullptr;
-  int copy_pending = 0;
+  MemberTable<RolloutMember> table;
 };
 
 namespace {
-std::string rmember_name(int m) { return "rollout group: member " + std::to_string(m); }
+std::string rmember_name(int m) { return group_member_name("rollout", m); }
 
 // the reward tables without what is per member (the record pointers)
 RewardArgs shape_reward(ddrl_ctx* c) {
@@ -2620,13 +2662,11 @@ RewardArgs shape_reward(ddrl_ctx* c) {
 int rgroup_same_shape(ddrl_ctx* a, ddrl_ctx* b, int m) {
   const ddrl_cfg &x = a->cfg, &y = b->cfg;
   const char* why = nullptr;
-#define DDRL_RGRP_SAME(f) if (!why && !(x.f == y.f)) why = #f
-  DDRL_RGRP_SAME(model_kind); DDRL_RGRP_SAME(n_envs); DDRL_RGRP_SAME(frag_len); DDRL_RGRP_SAME(n_policies);
-  DDRL_RGRP_SAME(n_agents); DDRL_RGRP_SAME(act_dim); DDRL_RGRP_SAME(obs_full_dim); DDRL_RGRP_SAME(leg_coupling);
-  DDRL_RGRP_SAME(policy_filter); DDRL_RGRP_SAME(filter_enabled); DDRL_RGRP_SAME(filter_update);
-  DDRL_RGRP_SAME(filter_clip); DDRL_RGRP_SAME(reward_mode); DDRL_RGRP_SAME(ctrl_cost_weight);
-  DDRL_RGRP_SAME(contact_cost_weight);
-#undef DDRL_RGRP_SAME
+  DDRL_GRP_SAME(model_kind); DDRL_GRP_SAME(n_envs); DDRL_GRP_SAME(frag_len); DDRL_GRP_SAME(n_policies);
+  DDRL_GRP_SAME(n_agents); DDRL_GRP_SAME(act_dim); DDRL_GRP_SAME(obs_full_dim); DDRL_GRP_SAME(leg_coupling);
+  DDRL_GRP_SAME(policy_filter); DDRL_GRP_SAME(filter_enabled); DDRL_GRP_SAME(filter_update);
+  DDRL_GRP_SAME(filter_clip); DDRL_GRP_SAME(reward_mode); DDRL_GRP_SAME(ctrl_cost_weight);
+  DDRL_GRP_SAME(contact_cost_weight);
   for (int p = 0; p < x.n_policies && !why; ++p) {
     const Policy &P = a->pol[p], &Q = b->pol[p];
     if (P.d != Q.d) why = "obs_dim";
@@ -2639,9 +2679,9 @@ int rgroup_same_shape(ddrl_ctx* a, ddrl_ctx* b, int m) {
     const RewardArgs ra = shape_reward(a), rb = shape_reward(b);
     if (std::memcmp(&ra, &rb, sizeof(RewardArgs)) != 0) why = "the reward tables (n_contact, contact_index, contact_weight)";
   }
-  if (why) return fail(rmember_name(m) + " differs from member 0 in " + why + ": a group takes contexts of one shape");
-  return 0;
+  return group_same_result("rollout", m, why);
 }
+#undef DDRL_GRP_SAME
 
 // what a member and its env must still be at every run (create checks it too)
 int rgroup_member_ok(const ddrl_rollout_group* g, int m) {
@@ -2660,9 +2700,7 @@ int rgroup_member_ok(const ddrl_rollout_group* g, int m) {
 }
 
 void rgroup_free(ddrl_rollout_group* g) {
-  if (g->copied) (void)hipEventDestroy(g->copied);
-  if (g->table_host) (void)hipHostFree(g->table_host);
-  if (g->table_dev) (void)hipFree(g->table_dev);
+  g->table.release();
   delete g;
 }
 }  // namespace
@@ -2675,14 +2713,7 @@ int ddrl_rollout_group_create(ddrl_ctx* const* members, ddrl_devenv* const* envs
   if (n_members < 1) return fail("rollout group: at least one member is needed");
   if (n_members > 65535)
     return fail("rollout group: " + std::to_string(n_members) + " members exceed the grid's z extent (65535)");
-  for (int m = 0; m < n_members; ++m) {
-    if (!members[m]) return fail(rmember_name(m) + " is a null context");
-    if (!envs[m]) return fail(rmember_name(m) + " has a null device env");
-    for (int k = 0; k < m; ++k) {
-      if (members[k] == members[m]) return fail(rmember_name(m) + " repeats member " + std::to_string(k));
-      if (envs[k] == envs[m]) return fail(rmember_name(m) + " repeats the device env of member " + std::to_string(k));
-    }
-  }
+  if (group_list_ok("rollout", members, envs, n_members)) return -1;
   ddrl_ctx* c0 = members[0];
   HIPCHK(hipSetDevice(c0->device));
   ddrl_rollout_group* g = new ddrl_rollout_group();
@@ -2691,20 +2722,11 @@ int ddrl_rollout_group_create(ddrl_ctx* const* members, ddrl_devenv* const* envs
   g->device = c0->device;
   g->stream = c0->stream;
   int rc = 0;
-  for (int m = 0; m < n_members && !rc; ++m) {
-    ddrl_ctx* c = members[m];
-    if (c->device != g->device) rc = fail(rmember_name(m) + " is on another device than member 0");
-    else if (c->cfg.model_kind != DDRL_MODEL_FFN) rc = fail(rmember_name(m) + " is a GraphNet context: the group rollout runs the fcnet kernels only");
-    else rc = rgroup_same_shape(c, c0, m);
-  }
+  for (int m = 0; m < n_members && !rc; ++m)
+    rc = group_member_kind("rollout", members[m], g->device, m) || rgroup_same_shape(members[m], c0, m);
   for (int m = 0; m < n_members && !rc; ++m) rc = rgroup_member_ok(g, m);
-  if (!rc) {
-    const size_t bytes = sizeof(RolloutMember) * (size_t)n_members;
-    if (hipHostMalloc((void**)&g->table_host, bytes, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void**)&g->table_dev, bytes) != hipSuccess || hipMemset(g->table_dev, 0, bytes) != hipSuccess ||
-        hipEventCreateWithFlags(&g->copied, hipEventDisableTiming) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-      rc = fail("rollout group: allocation of the member table failed");
-  }
+  if (!rc && (!g->table.alloc(n_members) || hipDeviceSynchronize() != hipSuccess))
+    rc = fail("rollout group: allocation of the member table failed");
   if (rc) {
     rgroup_free(g);
     return -1;
@@ -2727,14 +2749,11 @@ int ddrl_rollout_group_run(ddrl_rollout_group* g, const float* const* eps_dev, i
   if (reset)
     for (int m = 0; m < M; ++m)
       if (ddrl_devenv_reset(g->envs[m]) || ddrl_observe(g->members[m], g->envs[m]->a.obs)) return -1;
-  // the pinned table is the source of the previous run's H2D copy: wait for that copy before rewriting it
-  if (g->copy_pending) {
-    HIPCHK(hipEventSynchronize(g->copied));
-    g->copy_pending = 0;
-  }
+  RolloutMember* table = nullptr;
+  if (g->table.host(table)) return -1;
   for (int m = 0; m < M; ++m) {
     ddrl_ctx* c = g->members[m];
-    RolloutMember& r = g->table_host[m];
+    RolloutMember& r = table[m];
     r = RolloutMember{};
     for (int p = 0; p < cfg.n_policies; ++p) {
       Policy& P = c->pol[p];
@@ -2748,11 +2767,9 @@ int ddrl_rollout_group_run(ddrl_rollout_group* g, const float* const* eps_dev, i
     r.zs = c->zs;
     r.env = g->envs[m]->a;
   }
-  HIPCHK(hipMemcpyAsync(g->table_dev, g->table_host, sizeof(RolloutMember) * (size_t)M, hipMemcpyHostToDevice, g->stream));
-  HIPCHK(hipEventRecord(g->copied, g->stream));
-  g->copy_pending = 1;
+  if (g->table.upload(g->stream, M)) return -1;
   RolloutGroupArgs ga{};
-  ga.tab = g->table_dev; ga.M = M; ga.n = cfg.n_envs; ga.T = cfg.frag_len;
+  ga.tab = g->table.dev; ga.M = M; ga.n = cfg.n_envs; ga.T = cfg.frag_len;
   for (int p = 0; p < cfg.n_policies; ++p) {
     ga.lay[p] = c0->pol[p].lay;
     ga.C[p] = c0->pol[p].C;

@@ -21,63 +21,21 @@
 // ------------------------------------------------------------------------------------
 template <int A, int KS1>
 __global__ void __launch_bounds__(256) k_eval_act(RouteArgs ra, EvalActArgs ea) {
-  constexpr int O = 2 * A;
-  extern __shared__ float lds[];
   filter_count(ea.fc);
-  const int p = blockIdx.y;
-  const PolicyRoute& pr = ra.pol[p];
-  const int row_hi = ra.N * pr.k;
-  const int row0 = blockIdx.x * 64;
-  if (row0 >= row_hi) return;
-  const int d = pr.d;
-  const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4, w = threadIdx.x >> 6;
-  const int row = row0 + 16 * w + c;
-  const bool valid = row < row_hi;
-  const int rv = valid ? row : 0;
-  const int e = rv / pr.k, slot = rv - e * pr.k;
-  const float* o = ea.in.obs + (size_t)e * ra.full_dim;
-  const double* P = policy_filter_normc(ea.in.pf, p);
-  float xop[12];
-#pragma unroll
-  for (int s = 0; s < 12; ++s) {
-    const int f = 4 * s + q;
-    float v = 0.f;
-    if (s < KS1 && f < d && valid) v = routed_input(pr, slot, f, o, ea.in.normc, ea.in.clip, P);
-    xop[s] = v;
-  }
-  // the weights are staged after the operand loads were issued: the fp64 normalization runs
-  // while the weight loads are in flight
-  NetLds PW;
-  stage_policy_weights(ea.in.theta[p], d, A, lds, PW, 256);
-  __syncthreads();
-  floatx4 h1[4], h2[4];
-  float logits[O];
-  ffn_branch_fwd<O, KS1>(PW, xop, h1, h2, logits);
-  if (!valid) return;
-  const int agent = pr.agent[slot];
-  // "cup" model: mean_j *= coupling[leg][j], leg = the agent's slot (k_act_ffn).  In place in each
-  // kernel: through a shared helper the A = 2 instances of this one measured 0.2 us longer
-  if (ea.in.cup[p]) {
-#pragma unroll
-    for (int j = 0; j < A; ++j) logits[j] *= ea.in.cup[p][slot * A + j];
-  }
-  if (q == 0) {
-#pragma unroll
-    for (int j = 0; j < A; ++j) {
-      const float mu = logits[j], ls = logits[A + j];
-      float act = mu;   // deterministic: the DiagGaussian mean (explore=False)
-      if (ea.eps) {
-        const float sd = expf(ls);
-        const float eps = ea.eps[((size_t)e * ra.n_agents + agent) * A + j];
-        act = mu + sd * eps;
-      }
-      scatter_action(ea.actions, pr, e, slot, j, act);
-    }
-  } else if (q == 1 && ea.logits_out[p]) {
-    float* lo = ea.logits_out[p] + (size_t)row * O;
-#pragma unroll
-    for (int j = 0; j < O; ++j) lo[j] = logits[j];
-  }
+  // eval_<field>: where the plain arguments keep that operand; policy p's are macros (p is the text's)
+  const auto &eval_obs = ea.in.obs, &eval_eps = ea.eps;
+  const auto &eval_normc = ea.in.normc, &eval_pf = ea.in.pf;
+  const auto& eval_clip = ea.in.clip;
+  const auto& eval_actions = ea.actions;
+#define eval_theta ea.in.theta[p]
+#define eval_cup ea.in.cup[p]
+#define eval_logits_out ea.logits_out[p]
+#define EVAL(field) eval_##field
+#define EVAL_TILE_GUARD
+#include "eval_act_body.h"
+#undef eval_theta
+#undef eval_cup
+#undef eval_logits_out
 }
 
 template <int A, int KS1>

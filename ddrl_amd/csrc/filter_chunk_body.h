@@ -1,5 +1,5 @@
-// The body of k_filter_chunk (rollout.hip) and k_filter_chunk_group (rollout_group.hip), included
-// inside the kernel's braces.  Operands by name: obs [N][D], N, D, part (the chunk scratch).
+// The body of k_filter_chunk (rollout.hip), k_filter_chunk_group (rollout_group.hip) and
+// k_filter_chunk_members (eval_members.hip), included inside the kernel's braces.  Operands by name: obs [N][D], N, D, part (the chunk scratch).
   const int j = blockIdx.x, sc = blockIdx.y;
   __shared__ double red[4];
   const int tid = threadIdx.x, w = tid >> 6;

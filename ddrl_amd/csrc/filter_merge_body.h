@@ -1,5 +1,5 @@
-// The body of k_filter_merge (rollout.hip) and k_filter_merge_group (rollout_group.hip), included inside the
-// kernel's braces.  Operands: N, D, part, the running (n_run, M, S) and delta (dn, dM, dS) stat, normc, push, enabled.
+// The body of k_filter_merge (rollout.hip), k_filter_merge_group (rollout_group.hip) and k_filter_merge_members
+// (eval_members.hip), included inside the kernel's braces.  The counts are advanced by the kernel behind it.  Operands: N, D, part, the running (n_run, M, S) and delta (dn, dM, dS) stat, normc, push, enabled.
   const int j = threadIdx.x;
   if (j >= D) return;
   double n1 = n_run[0];

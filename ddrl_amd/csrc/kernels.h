@@ -162,7 +162,7 @@ struct EvalMembersArgs {
   size_t theta_stride[DDRL_MAXP];  // floats from one member's parameters to the next
   int cup_off[DDRL_MAXP];          // offset of the "cup" table [4][A] in the parameters (< 0: none)
   const float* obs;                // raw observations [M n][full_dim]
-  const double* filt;              // [M][FM_STRIDE]
+  double* filt;                    // [M][FM_STRIDE]; the act kernel advances the counts
   const double* pf;                // [M][P][PF_STRIDE] per-policy filter state, or nullptr
   size_t pf_stride;                // doubles per member
   float clip;
@@ -170,11 +170,12 @@ struct EvalMembersArgs {
   const float* eps;                // [M n][n_agents][A] or nullptr
   float* actions;                  // [M n][8]
 };
-// ra.N = n, the envs of ONE member; grid (ceil(n k_max / 64), P, M)
-void launch_eval_act_members(hipStream_t s, const RouteArgs& ra, const EvalMembersArgs& ma, int n_members);
+// ra.N = n, the envs of ONE member; grid (ceil(n k_max / 64), P, M).  count: the batch count of this
+// step's env-side filter push (0: none), added to every member's counts as FilterCount's is
+void launch_eval_act_members(hipStream_t s, const RouteArgs& ra, const EvalMembersArgs& ma, int n_members, int count);
 // launch_filter_push with a member index in the grid: chunks counted from the member's first env,
-// merged in order; the count of a pushed batch is added by the merge kernel itself, after every
-// column has read it.  part: n_members * filter_part_doubles(n, D) doubles
+// merged in order; the count of a pushed batch is left to launch_eval_act_members behind it.
+// part: n_members * filter_part_doubles(n, D) doubles
 void launch_filter_push_members(hipStream_t s, const float* obs, int n, int D, int n_members, double* filt,
                                 int update, int enabled, double* part);
 

@@ -158,12 +158,23 @@ def test_member_act_parity(env, M, n, config):
     _close(mctx, *plain)
 
 
-def test_member_filter_continues():
+FILTER_CASES = [
+    pytest.param(LOCAL, 2, 260, None, id="local_2x260"),   # two chunks per member, the second ragged
+    # D = 44: the merge kernel's 44th column is live; the second chunk is a single row; member 1 is
+    # neither the first nor the last z, where a count added once per launch or to a neighbour would show
+    pytest.param("QuantrupedMultiEnv_FullyDecentral", 3, 257, {"env_config": {"target_velocity": [1.0]}},
+                 id="tvel_3x257"),
+]
+
+
+@pytest.mark.parametrize("env,M,n,config", FILTER_CASES)
+def test_member_filter_continues(env, M, n, config):
     """filter_update = 1 over three steps, two chunks per member (the second ragged): the actions of
-    every step and the final running stat of every member are those of its plain context."""
+    every step and the final running stat of every member are those of its plain context, and the
+    count of every member (advanced by the act kernel behind the merge) is exactly 3 n further."""
     import torch
-    M, n = 2, 260
-    mctx, cfg, plain = _members(LOCAL, M, n, None, filter_update=True)
+    mctx, cfg, plain = _members(env, M, n, config, filter_update=True)
+    assert cfg.obs_full_dim == (44 if config else 43)
     own = _own_state(mctx, cfg)
     rng = np.random.default_rng(32)
     act_m = torch.full((M * n, 8), float("nan"), dtype=torch.float32, device="cuda")
