@@ -293,6 +293,31 @@ void launch_rollout_group_step(hipStream_t s, const RouteArgs& ra, const RewardA
 // V(s_T) of every member into last_v
 void launch_rollout_group_bootstrap(hipStream_t s, const RouteArgs& ra, const RolloutGroupArgs& ga);
 
+// ---- device randomness (rng.hip; the generator and the layouts: philox.h) ----
+// What differs between the members of a group fill is one entry of a device table, indexed by
+// blockIdx.z; the solo kernels take the same struct by value.  The shapes are equal for all members.
+struct NoiseMember {
+  float* eps;                      // [n_steps][N][n_agents][A], 16-byte aligned
+  unsigned long long seed, pos;    // the noise stream: its seed and the absolute step of eps[0]
+};
+// B: Philox blocks per env (n_agents * A / 4); one lane per block, one 16-byte store per lane
+void launch_noise_fill(hipStream_t s, const NoiseMember& nm, int n_steps, int N, int B);
+void launch_noise_fill_group(hipStream_t s, const NoiseMember* tab_dev, int M, int n_steps, int N, int B);
+struct ScheduleMember {
+  int32_t* shuffle[DDRL_MAXP];     // [R_p]
+  int32_t* perm[DDRL_MAXP];        // [epochs][nb_p]
+  unsigned long long seed, draw;   // the schedule stream: its seed and the index of this draw
+};
+struct ScheduleShape {
+  int n_pol;                       // policies filled by the launch (the set bits of the mask) ...
+  int pid[DDRL_MAXP];              // ... and their ids: blockIdx.y indexes this list
+  int R[DDRL_MAXP], nb[DDRL_MAXP]; // by policy id
+  int epochs;
+};
+// one lane per element of shuffle | perm[0] | perm[1] | ... of every filled policy
+void launch_schedule_fill(hipStream_t s, const ScheduleMember& sm, const ScheduleShape& sh);
+void launch_schedule_fill_group(hipStream_t s, const ScheduleMember* tab_dev, int M, const ScheduleShape& sh);
+
 // ---- PPO update (fused persistent minibatch loop) ----
 struct UpdateArgs {
   const float* rec; RecLayout lay;

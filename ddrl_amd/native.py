@@ -22,6 +22,8 @@ REWARD_PER_LEG, REWARD_GLOBAL, REWARD_NORM = 0, 1, 2
 VF_CLIP_RAY10, VF_CLIP_SQUARED = 0, 1
 # message-passing layer of the "gnn" model (models/graph_net.py:20 selects one of models/gcn.py's)
 GNN_LAYERS = {"mpnn": 0, "gcn": 1, "mpnn2": 2, "gat1": 3}
+RNG_NOISE, RNG_SCHEDULE = 0, 1   # DDRL_RNG_*: the two streams of a context's device generator
+_U64 = (1 << 64) - 1
 
 i32, f32 = C.c_int32, C.c_float
 
@@ -183,6 +185,13 @@ _SIGS = {
     "ddrl_rollout_group_create": ([C.POINTER(VP), C.POINTER(VP), C.c_int, C.POINTER(VP)], C.c_int),
     "ddrl_rollout_group_run": ([VP, C.POINTER(VP), C.c_int], C.c_int),
     "ddrl_rollout_group_destroy": ([VP], C.c_int),
+    "ddrl_rng_seed": ([VP, C.c_int, C.c_uint64], C.c_int),
+    "ddrl_rng_state_get": ([VP, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
+    "ddrl_rng_state_set": ([VP, C.c_int, C.c_uint64, C.c_uint64], C.c_int),
+    "ddrl_noise_fill": ([VP, C.c_int, VP], C.c_int),
+    "ddrl_schedule_fill": ([VP, C.c_int, C.POINTER(VP), C.POINTER(VP)], C.c_int),
+    "ddrl_noise_fill_group": ([C.POINTER(VP), C.c_int, C.c_int, C.POINTER(VP)], C.c_int),
+    "ddrl_schedule_fill_group": ([C.POINTER(VP), C.c_int, C.POINTER(VP), C.POINTER(VP)], C.c_int),
 }
 
 _lib = None
@@ -660,6 +669,43 @@ class Context:
         _ck(self.lib.ddrl_policy_forward(self.h, pid, _ptr(obs_dev), _ptr(node_dev), n,
                                          _ptr(logits_dev), _ptr(values_dev)))
 
+    # ---- device randomness: noise and schedules drawn by the counter-based generator ----
+    def rng_seed(self, stream, seed):
+        """Seed the RNG_NOISE or RNG_SCHEDULE stream (any Python int, taken modulo 2^64); its
+        position restarts at 0."""
+        _ck(self.lib.ddrl_rng_seed(self.h, int(stream), int(seed) & _U64))
+
+    def rng_state(self, stream):
+        """(seed, position) of the stream: all of its state."""
+        s, pos = C.c_uint64(), C.c_uint64()
+        _ck(self.lib.ddrl_rng_state_get(self.h, int(stream), C.byref(s), C.byref(pos)))
+        return int(s.value), int(pos.value)
+
+    def rng_state_set(self, stream, seed, position):
+        _ck(self.lib.ddrl_rng_state_set(self.h, int(stream), int(seed) & _U64, int(position) & _U64))
+
+    def noise_fill(self, n_steps, eps_dev):
+        """eps_dev [n_steps, N, n_agents, A] float32 <- the next n_steps steps of the noise stream."""
+        _ck(self.lib.ddrl_noise_fill(self.h, int(n_steps), _ptr(eps_dev)))
+
+    def schedule_alloc(self, device=None):
+        """Persistent device arrays for schedule_fill: (shuffles, perms), per policy int32 [R_p] and
+        [num_sgd_iter, nb_p], the shapes ppo_update takes."""
+        import torch
+        dev = torch.device("cuda", self.device) if device is None else device
+        mb, T, E = self.cfg.sgd_minibatch_size, self.cfg.frag_len, self.cfg.num_sgd_iter
+        R = [T * self.layout[p]["C"] for p in range(self.cfg.n_policies)]
+        return ([torch.empty(r, dtype=torch.int32, device=dev) for r in R],
+                [torch.empty((E, max(1, r // mb)), dtype=torch.int32, device=dev) for r in R])
+
+    def schedule_fill(self, shuffles, perms, mask=None):
+        """The next draw of the schedule stream into the policies of `mask` (default: all)."""
+        P = self.cfg.n_policies
+        mask = (1 << P) - 1 if mask is None else int(mask)
+        sh = (VP * MAX_P)(*[_ptr(shuffles[p]) if p < len(shuffles) else None for p in range(MAX_P)])
+        pe = (VP * MAX_P)(*[_ptr(perms[p]) if p < len(perms) else None for p in range(MAX_P)])
+        _ck(self.lib.ddrl_schedule_fill(self.h, mask, sh, pe))
+
 
 def _terrain_args(lo, hi, generation, current_generation):
     """(lo, hi, generation) of a set_terrain call: hi None is lo, generation None the current one."""
@@ -678,6 +724,31 @@ def _terrain_points(env_index, xy, n_envs):
     if idx.size and (idx.min() < 0 or idx.max() >= n_envs):
         raise DdrlError(f"terrain_height: env index out of range [0, {n_envs})")
     return idx, pts
+
+
+def noise_fill_group(contexts, n_steps, eps_devs):
+    """Context.noise_fill for every member in one launch (ddrl_noise_fill_group): eps_devs[m] is
+    member m's buffer; every member's noise stream advances by n_steps."""
+    cs, eps = list(contexts), list(eps_devs)
+    if len(cs) != len(eps):
+        raise DdrlError(f"noise fill group: {len(cs)} contexts and {len(eps)} noise buffers")
+    n = len(cs)
+    _ck(load().ddrl_noise_fill_group((VP * max(1, n))(*[c.h for c in cs]), n, int(n_steps),
+                                     (VP * max(1, n))(*[_ptr(x) for x in eps])))
+
+
+def schedule_fill_group(contexts, shuffles, perms):
+    """Context.schedule_fill of all policies for every member in one launch
+    (ddrl_schedule_fill_group): shuffles / perms hold one list per member, one entry per policy."""
+    cs = list(contexts)
+    P = cs[0].cfg.n_policies if cs else 0
+    flat = lambda xs: [x for member in xs for x in list(member)[:P]]
+    sh, pe = flat(shuffles), flat(perms)
+    n = len(cs) * P
+    if not (len(sh) == len(pe) == n):
+        raise DdrlError(f"schedule fill group: {n} (member, policy) entries expected")
+    _ck(load().ddrl_schedule_fill_group((VP * max(1, len(cs)))(*[c.h for c in cs]), len(cs),
+                                        (VP * max(1, n))(*[_ptr(x) for x in sh]), (VP * max(1, n))(*[_ptr(x) for x in pe])))
 
 
 def update_group_grid(n_chains):

@@ -8,7 +8,10 @@ context, envs, noise, schedule, filters, KL coefficients and results -- with the
 of an iteration replaced by one.  On the device env plane the members' fragments are one chain of
 launches too (native.RolloutGroup, csrc/rollout_group.hip), each member drawing its noise from its
 own generator as the solo trainer does; GAE and the episode accounting stay per member.  On the
-synthetic and host planes sampling stays per member, in stream order.
+synthetic and host planes sampling stays per member, in stream order.  With rng_backend "device"
+every member's generator is its context's pair of device streams, and the members' noise slabs
+and schedules are one group launch each (native.noise_fill_group, native.schedule_fill_group)
+instead of host draws member by member.
 """
 from __future__ import annotations
 
@@ -48,6 +51,8 @@ class PopulationTrainer:
                 if t.world != 1 or t.parallel != "replicas":
                     raise ValueError(f"PopulationTrainer: parallel {t.parallel!r} over {t.world} process(es); a "
                                      "population is single-process replicas")
+            # rng_backend "device" (one config: all members or none): group fills replace the host draws
+            self.device_rng = bool(self.trainers) and self.trainers[0].rng_backend == "device"
             self.group = N.UpdateGroup([t.ctx for t in self.trainers], max_chains_per_launch)
             self._init_group_rollout(group_rollout)
         except Exception:
@@ -68,16 +73,23 @@ class PopulationTrainer:
             raise ValueError("PopulationTrainer: group_rollout needs every member on the device env plane "
                              "(env_backend: 'device'); the synthetic and host planes sample member by member")
         self.rollout_group = N.RolloutGroup([t.rctx for t in self.trainers], [t.backend.env for t in self.trainers])
-        # every member's noise of a fragment, [T, n_envs, n_agents, A]: filled step by step from the
-        # member's own generator (the solo trainer's draw sequence), read by the group chain
-        self.noise = [self.torch.empty((t.T, t.n_envs, t.cfg.n_agents, t.cfg.act_dim), dtype=self.torch.float32,
-                                       device=self.device) for t in self.trainers]
+        # every member's noise of a fragment, [T, n_envs, n_agents, A], read by the group chain: filled
+        # step by step from the member's own generator (the solo trainer's draw sequence), or, with
+        # rng_backend "device", the members' own slabs filled by one group launch
+        if self.device_rng:
+            self.noise = [t.noise for t in self.trainers]
+        else:
+            self.noise = [self.torch.empty((t.T, t.n_envs, t.cfg.n_agents, t.cfg.act_dim), dtype=self.torch.float32,
+                                           device=self.device) for t in self.trainers]
 
     def _sample_group(self):
         torch = self.torch
-        for t, slab in zip(self.trainers, self.noise):
-            for step in range(t.T):
-                torch.randn(tuple(slab.shape[1:]), generator=t.noise_gen, out=slab[step])
+        if self.device_rng:
+            N.noise_fill_group([t.rctx for t in self.trainers], self.trainers[0].T, self.noise)
+        else:
+            for t, slab in zip(self.trainers, self.noise):
+                for step in range(t.T):
+                    torch.randn(tuple(slab.shape[1:]), generator=t.noise_gen, out=slab[step])
         self.rollout_group.run(self.noise)
         for t in self.trainers:
             t._sample_finish()
@@ -92,7 +104,10 @@ class PopulationTrainer:
                 t._sample()
         self.torch.cuda.synchronize(self.device)
         t1 = time.perf_counter()
-        sched = [t._learn_schedules() for t in self.trainers]
+        if self.device_rng:   # every member's schedule in one launch, into its own persistent arrays
+            N.schedule_fill_group([t.ctx for t in self.trainers], [t.sched[0] for t in self.trainers],
+                                  [t.sched[1] for t in self.trainers])
+        sched = [t._learn_schedules(fill=False) for t in self.trainers]
         self.group.run([s[0] for s in sched], [s[1] for s in sched], [t.kl_coeff for t in self.trainers])
         self.group.finish()
         learners = [t._learn_results(s[2]) for t, s in zip(self.trainers, sched)]

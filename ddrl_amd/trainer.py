@@ -91,6 +91,18 @@ class PPOTrainer:
         self.n_envs = int(n_envs or c.get("num_envs", c.get("num_workers", 2) * c.get("num_envs_per_worker", 4)))
         self.T = int(c["rollout_fragment_length"])
         self.cfg, self.env = make_cfg(env, self.n_envs, self.T, c)
+        self.parallel = c.get("parallel") or ("ddp" if self.world > 1 and self.cfg.n_policies == 1 else "replicas")
+        if self.parallel not in ("ddp", "replicas", "gather"):
+            raise ValueError(f"parallel {self.parallel!r}: 'ddp', 'replicas' or 'gather'")
+        # extension: "rng_backend": "device" draws the exploration noise and the minibatch schedules
+        # on the device from a counter-based generator (csrc/rng.hip) instead of torch / numpy on the
+        # host; "host" (the default) is the path as it always was
+        self.rng_backend = c.get("rng_backend", "host")
+        if self.rng_backend not in ("host", "device"):
+            raise ValueError(f"rng_backend {self.rng_backend!r}: 'host' or 'device'")
+        if self.rng_backend == "device" and self.parallel == "ddp":
+            raise ValueError("rng_backend 'device' does not cover parallel 'ddp': its learners draw their own "
+                             "schedule on the host; use rng_backend 'host', or parallel 'replicas' / 'gather'")
         torch.cuda.set_device(device)
         self.device = torch.device("cuda", device)
         self.stream = stream or torch.cuda.current_stream(self.device)
@@ -139,9 +151,6 @@ class PPOTrainer:
         self.noise_gen.manual_seed(noise_seed)
         self.timesteps_total = 0
         self.iteration = 0
-        self.parallel = c.get("parallel") or ("ddp" if self.world > 1 and P == 1 else "replicas")
-        if self.parallel not in ("ddp", "replicas", "gather"):
-            raise ValueError(f"parallel {self.parallel!r}: 'ddp', 'replicas' or 'gather'")
         self.rctx = self.ctx   # the rollout context (the learner's own, except in "gather" mode)
         self.episode_history = EpisodeHistory(int(c["metrics_smoothing_episodes"]))
         self.episodes_total = 0
@@ -160,6 +169,9 @@ class PPOTrainer:
                                  if self.cfg.policy_filter else None)
             self.rctx.policy_filter_delta_reset()
             self.sched_rng = np.random.default_rng(seed + 7919)   # the same schedule on every rank
+        if self.rng_backend == "device":
+            # the seeds of the host generators: noise_seed on the rollout context, sched_rng's on the learner
+            self._init_device_rng(noise_seed, seed + 7919 * (1 if self.parallel == "gather" else self.rank + 1))
         if self.parallel == "ddp":
             from .ddp import (Comm, DataParallelLearner, HipBackend, NativeDataParallelLearner, PeerLearner,
                               native_comm_init)
@@ -203,14 +215,33 @@ class PPOTrainer:
         self._sample_fragment()
         self._sample_finish()
 
+    def _init_device_rng(self, noise_seed, sched_seed):
+        """rng_backend "device": seed the two streams and allocate what they fill -- one noise slab
+        [T, N, agents, A] of a whole fragment and the learner's persistent schedule arrays."""
+        from .envs import DeviceVecEnv
+        torch, cfg = self.torch, self.cfg
+        self.rctx.rng_seed(N.RNG_NOISE, noise_seed)
+        self.ctx.rng_seed(N.RNG_SCHEDULE, sched_seed)
+        self.noise = torch.empty((self.T, self.n_envs, cfg.n_agents, cfg.act_dim), dtype=torch.float32,
+                                 device=self.device)
+        self.sched = self.ctx.schedule_alloc(self.device)
+        # on the device env plane the fragment is one chain (ddrl_rollout_devenv); False runs the
+        # per-step loop over the same slab (the same results; the other planes always do)
+        self.fragment_chain = isinstance(self.backend, DeviceVecEnv)
+
     def _sample_fragment(self):
-        """The fragment loop: T steps of act / env step / reward / observe, then the bootstrap.
+        """The fragment: T steps of act / env step / reward / observe, then the bootstrap.
         (A population replaces its members' loops by one group chain: ddrl_amd.population.)"""
         torch, cfg = self.torch, self.cfg
         rctx = self.rctx
+        if self.rng_backend == "device":
+            rctx.noise_fill(self.T, self.noise)
+            if self.fragment_chain:   # the slab's address is fixed: the captured graph is replayed
+                rctx.rollout_devenv(self.backend.env, self.noise)
+                return
         for t in range(self.T):
-            eps = torch.randn((self.n_envs, cfg.n_agents, cfg.act_dim), device=self.device,
-                              generator=self.noise_gen)
+            eps = self.noise[t] if self.rng_backend == "device" else torch.randn(
+                (self.n_envs, cfg.n_agents, cfg.act_dim), device=self.device, generator=self.noise_gen)
             rctx.act(t, eps, self.actions)
             obs, fw, cfrc, done = self.backend.step(self.actions)
             rctx.reward(t, fw, cfrc, self.actions, done)
@@ -307,10 +338,16 @@ class PPOTrainer:
         self.ctx.ppo_update((1 << self.cfg.n_policies) - 1, sh, pe, self.kl_coeff)
         return self._learn_results(nbs)
 
-    def _learn_schedules(self):
+    def _learn_schedules(self, fill=True):
         """The part of the fused update before its launch: every policy's schedule on the device,
-        drawn from this trainer's sched_rng in policy order.  (shuffles, perms, minibatches per epoch)"""
+        drawn from this trainer's sched_rng in policy order.  (shuffles, perms, minibatches per epoch)
+        rng_backend "device": one fill of the persistent arrays from the learner context's schedule
+        stream (fill=False: a population has filled its members' arrays in one group launch)."""
         torch = self.torch
+        if self.rng_backend == "device":
+            if fill:
+                self.ctx.schedule_fill(*self.sched)
+            return self.sched[0], self.sched[1], [int(q.shape[1]) for q in self.sched[1]]
         sh, pe, nbs = [], [], []
         for p in range(self.cfg.n_policies):
             s, q, nb = self._schedule(p)
@@ -385,8 +422,8 @@ class PPOTrainer:
                     self.rctx.params_set(p, weights[pid])
 
     def save(self, path):
-        """Checkpoint: weights, Adam m/v/beta powers, KL coefficients, filter state (npz,
-        no pickle)."""
+        """Checkpoint: weights, Adam m/v/beta powers, KL coefficients, filter state and, with
+        rng_backend "device", the state of the noise and schedule streams (npz, no pickle)."""
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         arrs = {}
         for p, pid in enumerate(self.policy_ids):
@@ -401,8 +438,11 @@ class PPOTrainer:
             for p, pid in enumerate(self.policy_ids):
                 n, M, S = self.ctx.policy_filter_get(p)
                 arrs[f"{pid}/filter/n"], arrs[f"{pid}/filter/M"], arrs[f"{pid}/filter/S"] = np.array([n]), M, S
-        arrs["meta"] = np.frombuffer(json.dumps({"iteration": self.iteration,
-                                                 "timesteps_total": self.timesteps_total}).encode(), np.uint8)
+        meta = {"iteration": self.iteration, "timesteps_total": self.timesteps_total}
+        if self.rng_backend == "device":   # (seed, position) of both streams: all of the generator's state
+            meta["rng"] = {"noise": list(self.rctx.rng_state(N.RNG_NOISE)),
+                           "schedule": list(self.ctx.rng_state(N.RNG_SCHEDULE))}
+        arrs["meta"] = np.frombuffer(json.dumps(meta).encode(), np.uint8)
         np.savez(path, **arrs)
         return path
 
@@ -423,6 +463,9 @@ class PPOTrainer:
                                          z[f"{pid}/filter/S"])
         meta = json.loads(bytes(z["meta"]).decode())
         self.iteration, self.timesteps_total = meta["iteration"], meta["timesteps_total"]
+        if self.rng_backend == "device" and "rng" in meta:   # files without the streams keep the trainer's own
+            self.rctx.rng_state_set(N.RNG_NOISE, *meta["rng"]["noise"])
+            self.ctx.rng_state_set(N.RNG_SCHEDULE, *meta["rng"]["schedule"])
         self._after_load({})
 
     def _after_load(self, learner):

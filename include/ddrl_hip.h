@@ -539,6 +539,42 @@ int ddrl_rollout_group_create(ddrl_ctx* const* members, ddrl_devenv* const* envs
 int ddrl_rollout_group_run(ddrl_rollout_group* group, const float* const* eps_dev, int reset);
 int ddrl_rollout_group_destroy(ddrl_rollout_group* group);
 
+/* Device randomness (rng.hip): the exploration noise of a fragment and the minibatch schedules of an
+ * update drawn on the device by a counter-based generator, Philox4x32-10 (csrc/philox.h; the exact
+ * counter and key layout: DESIGN.md section 3, "Device randomness").  A context has two streams,
+ * each a 64-bit seed and a 64-bit position: a draw is a pure function of (seed, position, element),
+ * so it is the same solo, as a group member or in chunks, and the whole state is two integers.
+ * Opt-in: a context whose streams are never seeded behaves as before.  Any model kind (only shapes
+ * are read).  All calls are asynchronous on the context's stream.
+ *   rng_seed: the stream's seed; its position := 0.  rng_state_get / rng_state_set: (seed, position),
+ *     e.g. for a checkpoint; set also rewinds.  get on an unseeded stream is refused.
+ *   noise_fill: eps_dev[n_steps][N][n_agents][A] (16-byte aligned) standard normals for the absolute
+ *     steps [position, position + n_steps) of the noise stream; position += n_steps.  The value at
+ *     (step, env, agent, action) does not depend on N, n_steps or the launch geometry.  Needs
+ *     n_agents * A to be a multiple of 4 (it is 8 in every registered env).
+ *   schedule_fill: for every policy p in pid_mask, shuffle_dev[p] : int32[R_p] and perm_dev[p] :
+ *     int32[num_sgd_iter][nb_p] as ddrl_ppo_update takes them, each a keyed bijection of [0, n) (a
+ *     balanced Feistel network with Philox round functions, cycle-walked; no sort).  The key is
+ *     (schedule seed, draw index = position, policy, array); position += 1 per call.
+ *   noise_fill_group / schedule_fill_group: the same for n_members contexts of one shape in ONE
+ *     launch, the member in the grid's z and its operands in a device table filled from a pinned
+ *     host buffer (owned by members[0]); eps_dev[m] is member m's buffer, shuffle_dev / perm_dev
+ *     hold n_members * n_policies entries, member-major, and every policy is filled.  Each member
+ *     is left exactly as by its solo call: the buffers and the advanced position.  All members on
+ *     one device and one stream; a null or repeated member, another device, stream or shape is
+ *     refused naming the member.
+ * Refused with a message: an unseeded stream, null buffers, n_steps < 1, a policy bit outside the
+ * context, a misaligned noise buffer. */
+enum { DDRL_RNG_NOISE = 0, DDRL_RNG_SCHEDULE = 1 };
+int ddrl_rng_seed(ddrl_ctx* ctx, int stream, uint64_t seed);
+int ddrl_rng_state_get(ddrl_ctx* ctx, int stream, uint64_t* seed, uint64_t* position);
+int ddrl_rng_state_set(ddrl_ctx* ctx, int stream, uint64_t seed, uint64_t position);
+int ddrl_noise_fill(ddrl_ctx* ctx, int n_steps, float* eps_dev);
+int ddrl_schedule_fill(ddrl_ctx* ctx, int pid_mask, int32_t* const* shuffle_dev, int32_t* const* perm_dev);
+int ddrl_noise_fill_group(ddrl_ctx* const* members, int n_members, int n_steps, float* const* eps_dev);
+int ddrl_schedule_fill_group(ddrl_ctx* const* members, int n_members, int32_t* const* shuffle_dev,
+                             int32_t* const* perm_dev);
+
 /* Data-parallel (shared policy) primitives: gradient of (1/minibatch) * sum over the
  * given rows -> grad_dev[n_params]; after the caller's all-reduce (RCCL), apply clip +
  * Adam.  rows_dev holds n_rows (<= 128) record indices.  stats_step >= 0 also writes this

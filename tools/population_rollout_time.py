@@ -15,6 +15,13 @@ and whether the group beat the replays in every run by more than the replays' ow
     at (16, 80) and (16, 4096), group_rollout on and off, alternating.
   --parent-root DIR (a built checkout of the parent commit): the solo ddrl_rollout_devenv fragment
     and bench.py's headline on this tree and on the parent's, child processes, alternating.
+  --rng: instead of the above, the device generator (DESIGN.md section 3, "Device randomness";
+    default output profiles/population/rng_time.json).  Whole PopulationTrainer.train() iterations
+    with rng_backend "host" and "device", alternating in one process, at the --iterations sizes;
+    the fills alone (wall clock around a synchronized call): the two group fills against the host
+    draws they replace (M x T torch.randn calls; M x P numpy schedules and their uploads); and, with
+    --parent-root, the host backend's iterations on this tree and on the parent's, child processes,
+    alternating.
 Writes one JSON document (default profiles/population/rollout_time.json).
 """
 import argparse
@@ -140,6 +147,144 @@ def time_iterations(M, n_envs, T, repeats):
     return res
 
 
+def wall(fn):
+    """Milliseconds of fn between two synchronizations: host work and device work."""
+    import torch
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def time_rng_iterations(M, n_envs, T, repeats, backends=("host", "device")):
+    """Whole PopulationTrainer.train() iterations per rng_backend, alternating; the first is the warm-up."""
+    from ddrl_amd.population import PopulationTrainer
+    config = {"env": LOCAL, "env_backend": "device", "rollout_fragment_length": T}
+    pops = {b: PopulationTrainer(config if b == "host" else {**config, "rng_backend": b}, range(M), n_envs=n_envs)
+            for b in backends}
+    out = {b: {"iteration_ms": [], "sample_ms": [], "learn_ms": []} for b in pops}
+    for it in range(repeats + 1):
+        for b, pop in pops.items():
+            t0 = time.perf_counter()
+            r = pop.train()
+            dt = (time.perf_counter() - t0) * 1e3
+            if it:
+                out[b]["iteration_ms"].append(dt)
+                out[b]["sample_ms"].append(r[0]["timers"]["sample_time_ms"])
+                out[b]["learn_ms"].append(r[0]["timers"]["learn_time_ms"])
+    for pop in pops.values():
+        pop.stop()
+    return {"members": M, "envs": n_envs, "frag_len": T, "runs": out,
+            **{b: {k: summary(v) for k, v in d.items()} for b, d in out.items()}}
+
+
+def rng_verdict(res):
+    """device below host by more than the host backend's own spread, per timer."""
+    for k in ("iteration_ms", "sample_ms", "learn_ms"):
+        h, d = res["runs"]["host"][k], res["runs"]["device"][k]
+        spread = max(h) - min(h)
+        res[f"{k}_host_spread"] = spread
+        res[f"{k}_host_minus_device"] = statistics.median(h) - statistics.median(d)
+        res[f"{k}_device_below_host_by_more_than_its_spread"] = bool(res[f"{k}_host_minus_device"] > spread)
+    print(json.dumps({k: v for k, v in res.items() if k != "runs"}), flush=True)
+    return res
+
+
+def time_rng_fills(N, make_cfg, n_envs, T, M, repeats):
+    """The fills alone: the two group launches of the device generator against the host draws of the
+    same arrays (what PopulationTrainer issues per iteration with either backend)."""
+    import numpy as np
+    import torch
+    members, cfg = make_members(N, make_cfg, LOCAL, n_envs, T, M)
+    ctxs = [x[0] for x in members]
+    for m, ctx in enumerate(ctxs):
+        ctx.rng_seed(N.RNG_NOISE, 1000 + m)
+        ctx.rng_seed(N.RNG_SCHEDULE, 2000 + m)
+    slabs = [x[3] for x in members]
+    sched = [ctx.schedule_alloc() for ctx in ctxs]
+    rngs = [np.random.default_rng(m) for m in range(M)]
+    shape = (n_envs, cfg.n_agents, cfg.act_dim)
+    R = [T * ctxs[0].layout[p]["C"] for p in range(cfg.n_policies)]
+    nb = [max(1, r // cfg.sgd_minibatch_size) for r in R]
+
+    def host_noise():
+        for ctx, env_m, gen, slab, actions in members:
+            for t in range(T):
+                torch.randn(shape, generator=gen, out=slab[t])
+
+    def host_schedule():
+        keep = []
+        for rng in rngs:
+            for p in range(cfg.n_policies):
+                sh = rng.permutation(R[p]).astype(np.int32)
+                pe = np.stack([rng.permutation(nb[p]) for _ in range(cfg.num_sgd_iter)]).astype(np.int32)
+                keep.append((torch.from_numpy(sh).to("cuda"), torch.from_numpy(pe).to("cuda")))
+
+    variants = {"host_noise": host_noise, "noise_fill_group": lambda: N.noise_fill_group(ctxs, T, slabs),
+                "host_schedule": host_schedule,
+                "schedule_fill_group": lambda: N.schedule_fill_group(ctxs, [s[0] for s in sched], [s[1] for s in sched])}
+    for fn in variants.values():
+        fn()
+    ms = {k: [] for k in variants}
+    for _ in range(repeats):
+        for k, fn in variants.items():
+            ms[k].append(wall(fn))
+    for ctx, env_m, *_ in members:
+        env_m.close()
+        ctx.close()
+    res = {"members": M, "envs": n_envs, "frag_len": T, "unit": "milliseconds, wall clock around a synchronized call",
+           "runs": ms, **{f"{k}_ms": summary(v) for k, v in ms.items()}}
+    print(json.dumps({k: v for k, v in res.items() if k != "runs"}), flush=True)
+    return res
+
+
+def rng_child(root, sizes, T, repeats):
+    """Child process: the host backend's iterations on the tree at `root`; one JSON line."""
+    sys.path.insert(0, root)
+    print(json.dumps([time_rng_iterations(m, n, T, repeats, backends=("host",)) for m, n in sizes]))
+
+
+def rng_regression(a, sizes):
+    trees = (("this", HERE), ("parent", os.path.abspath(a.parent_root)))
+    runs = {n: [{k: [] for k in ("iteration_ms", "sample_ms", "learn_ms")} for _ in sizes] for n, _ in trees}
+    for rnd in range(a.rounds):
+        for name, root in (trees if rnd % 2 == 0 else trees[::-1]):
+            got = child_json([sys.executable, os.path.abspath(__file__), "--rng-child", root, "--iterations", a.iterations,
+                              "--frag-len", str(a.frag_len), "--repeats", str(a.repeats)], root, f"the rng child of {root}")
+            for i, g in enumerate(got):
+                for k, v in g["runs"]["host"].items():
+                    runs[name][i][k] += v
+    out = []
+    for i, (m, n) in enumerate(sizes):
+        out.append({"members": m, "envs": n,
+                    **{k: against({"this": runs["this"][i][k], "parent": runs["parent"][i][k]},
+                                  f"{k} of a host-backend PopulationTrainer.train(), Local {m} x {n}; {a.rounds} alternating "
+                                  f"processes per tree x {a.repeats}") for k in ("iteration_ms", "sample_ms", "learn_ms")}})
+    return out
+
+
+def main_rng(a):
+    sizes = [(int(m), int(n)) for m, n in (s.split(":") for s in a.iterations.split(",") if s)]
+    if a.rng_child:
+        return rng_child(a.rng_child, sizes, a.frag_len, a.repeats)
+    sys.path.insert(0, HERE)
+    import torch
+    from ddrl_amd import native as N
+    from ddrl_amd.spec import make_cfg
+    if not torch.cuda.is_available():
+        sys.exit("population_rollout_time: needs a GPU (no timing without one)")
+    out = a.out or os.path.join(HERE, "profiles", "population", "rng_time.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "commit": a.commit, "frag_len": a.frag_len, "repeats": a.repeats}
+    res["iterations"] = [rng_verdict(time_rng_iterations(m, n, a.frag_len, a.repeats)) for m, n in sizes]
+    res["fills"] = [time_rng_fills(N, make_cfg, n, a.frag_len, m, a.repeats) for m, n in sizes]
+    if a.parent_root:
+        res["host_backend_against_parent"] = rng_regression(a, sizes)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def solo_child(root, n_envs, T, repeats):
     """Child process: the solo ddrl_rollout_devenv fragment of Local on the tree at `root`; one JSON line."""
     sys.path.insert(0, root)
@@ -199,11 +344,16 @@ def main():
     ap.add_argument("--iterations", default="16:80,16:4096", help="members:envs of the whole-iteration timing ('' skips it)")
     ap.add_argument("--parent-root", default="", help="a built checkout of the parent commit (the solo regression)")
     ap.add_argument("--solo-child", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--rng", action="store_true", help="time the device generator (rng_backend host against device)")
+    ap.add_argument("--rng-child", default="", help=argparse.SUPPRESS)
     ap.add_argument("--commit", default="")
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "population", "rollout_time.json"))
+    ap.add_argument("--out", default="", help="default: profiles/population/rollout_time.json (rng_time.json with --rng)")
     a = ap.parse_args()
     if a.solo_child:
         return solo_child(a.solo_child, a.envs, a.frag_len, a.repeats)
+    if a.rng or a.rng_child:
+        return main_rng(a)
+    a.out = a.out or os.path.join(HERE, "profiles", "population", "rollout_time.json")
     sys.path.insert(0, HERE)
     import torch
     from ddrl_amd import native as N
