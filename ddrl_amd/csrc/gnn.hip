@@ -1034,7 +1034,7 @@ __device__ __forceinline__ void gnn_tail(const GnnArgs& ga, float* lds, int tile
   __builtin_amdgcn_s_waitcnt(0);   // this wave's partial / statistics stores are in L2
   __syncthreads();
   // arrival flag of tile `tile` of combination k: this launch's tag and this workgroup's XCC;
-  // the placement record for the host check (capi.cpp gnn_placement_broken)
+  // the placement record for the host check (capi_ctx.cpp gnn_placement_broken)
   if (tid == 0) {
     __hip_atomic_store(ga.flags + gnn_flag_idx(k, tile), (ga.tag << 4) | xcc, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_WORKGROUP);

@@ -1,6 +1,6 @@
 // f1: host env plane -- the clean-room vectorized QuAntruped stand-in and its thread pool
 // (see hostenv.h), plus the C-ABI to create / reset / step it.  The pipelined rollout over
-// it (ddrl_rollout_hostenv) lives in capi.cpp next to the context it drives.
+// it (ddrl_rollout_hostenv) lives in capi_rollout.cpp next to the context it drives.
 #include "hostenv.h"
 
 #include <hip/hip_runtime.h>

@@ -121,7 +121,7 @@ struct UpdateBatch {
   unsigned long long* xchg;  // [P][2 branches][KSP][2 parities] tagged norm^2 granules
   unsigned long long* gx;    // [P][2 branches][KSP][2 parities][GX_MAX_PAIRS][256 lanes][2] partial-gradient granules
   int* err;              // set to 1 if an exchange timed out
-  int* xcc;              // [grid] XCC id of every block (placement check, capi.cpp)
+  int* xcc;              // [grid] XCC id of every block (placement check, capi_ctx.cpp)
   unsigned epoch;        // launch counter (12 bits, never 0): high bits of every exchange tag
   unsigned lds_bytes;    // dynamic LDS of the launch (bounds-checked build)
   // -1: every row half runs here.  0 / 1 (peer mode, ddrl_ppo_update_peer): only that half runs
@@ -1547,7 +1547,7 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
 // blocks 32 (c >> 3) + 8 j + (c & 7), j = 2 branch + row half -- k_update_ffn's p + 8 j with a group
 // row every 32 blocks, so a chain's four workgroups stay congruent mod 8 (one XCD) and each XCD
 // holds four workgroups per group row.  Every workgroup spins on partners, so the whole grid must be
-// resident: the host sizes a launch to the device (capi.cpp, ddrl_update_group_create).  The chain's
+// resident: the host sizes a launch to the device (capi_group.cpp, ddrl_update_group_create).  The chain's
 // UpdateArgs come from a device table (64 chains do not fit the argument block) through wave-uniform
 // loads; the chain index takes the policy's place in update_loop's outbox and granule indexing, and
 // the step loop is the solo kernel's.
@@ -1561,7 +1561,7 @@ __global__ void __launch_bounds__(64 * waves_for(A, 2)) k_update_ffn_group(Group
   extern __shared__ float lds[];
   constexpr int NW = waves_for(A, 2);
   const int c = 8 * (int)(blockIdx.x >> 5) + (int)(blockIdx.x & 7);
-  if (threadIdx.x == 0) {   // placement record: XCC of every block (capi.cpp ddrl_update_group_finish)
+  if (threadIdx.x == 0) {   // placement record: XCC of every block (capi_group.cpp ddrl_update_group_finish)
     unsigned x;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
     gb.b.xcc[blockIdx.x] = (int)(x & 0xf);
@@ -1589,7 +1589,7 @@ __global__ void __launch_bounds__(64 * waves_for(A, KSP)) k_update_ffn(UpdateBat
   // one policy are dealt to the same XCD (b mod 8), so its per-step exchanges stay inside
   // one XCD (speed only; they are agent-scope either way).  Blocks with p >= P have no work.
   const int p = blockIdx.x & 7;
-  if (threadIdx.x == 0) {   // placement record: XCC of every block (capi.cpp check_placement)
+  if (threadIdx.x == 0) {   // placement record: XCC of every block (capi_ctx.cpp placement_broken)
     unsigned x;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
     ub.xcc[blockIdx.x] = (int)(x & 0xf);
@@ -1678,7 +1678,7 @@ void DDRL_FFN_LAUNCH(hipStream_t s, const UpdateArgs* ua, const UpdateHyper& h, 
                        int* err, unsigned* epoch_ctr, int* xcc, int own_kq, unsigned lx_base) {
 #if DDRL_MB == 256
   // only fused row-split launches of whole 256-row minibatches exist at this size.  The host
-  // (capi.cpp launch_ffn) sends nothing else here; were it to, the launch is dropped with the
+  // (capi_update.cpp launch_ffn) sends nothing else here; were it to, the launch is dropped with the
   // error word set, so the call fails and the state is restored: never another kernel in its place
   if (!(ksp == 2 && ua[0].grad_out == nullptr && own_kq < 0 && nrows == DDRL_MB)) {
     (void)hipMemsetD32Async((hipDeviceptr_t)err, 1, 1, s);
@@ -1733,7 +1733,7 @@ void DDRL_FFN_LAUNCH(hipStream_t s, const UpdateArgs* ua, const UpdateHyper& h, 
       }
     }
   }
-  if (cup)   // "cup": one shared leg policy, A = 2, d <= 20 (capi validate)
+  if (cup)   // "cup": one shared leg policy, A = 2, d <= 20 (capi_ctx.cpp validate)
     launch_update_t<2, 5, true>(s, ub, h.P, stride, ksp, lx);
   else
     DDRL_DISPATCH_A_KS1(A, d, launch_update_t, s, ub, h.P, stride, ksp, lx);

@@ -96,6 +96,36 @@ def test_native_ddp_loop_matches_python_learner(pg1, env, n, T, gnn, mode, gscal
     ctx_b.close()
 
 
+def test_native_ddp_buffers_grow_between_calls(pg1):
+    """ddrl_ppo_update_ddp keeps its gathered-record chunk and its slot list between calls and replaces them
+    when a longer schedule needs more room: one epoch (4 steps), then three (12 steps) on one context.  The
+    second call must leave what it leaves on a fresh context that is given the state before it and runs it
+    alone: parameters, Adam state and the last epoch's statistics, bit for bit."""
+    import torch
+    from ddrl_amd.ddp import Comm, native_comm_init
+    ctx_a, ctx_b = _pair("QuantrupedMultiEnv_SharedDecentral", 32, 4, False)
+    for ctx in (ctx_a, ctx_b):
+        native_comm_init(ctx, Comm("cpu"))
+    R = ctx_a.records_get(0).shape[0]
+    sh, pe = O.sgd_schedule(np.random.default_rng(7), R, 128, 1)
+    assert pe.shape == (1, 4)
+    ctx_a.ppo_update_ddp(0, torch.from_numpy(sh).cuda(), pe, 128, 0.2, 1.0)
+    before = ctx_a.params_get(0)
+    ctx_b.params_set(0, before)
+    ctx_b.adam_set(0, *ctx_a.adam_get(0))
+    sh, pe = O.sgd_schedule(np.random.default_rng(8), R, 128, 3)
+    sh_dev = torch.from_numpy(sh).cuda()
+    for ctx in (ctx_a, ctx_b):
+        ctx.ppo_update_ddp(0, sh_dev, pe, 128, 0.2, 1.0)
+    assert not np.array_equal(ctx_a.params_get(0), before)   # the second call trained
+    np.testing.assert_array_equal(ctx_a.params_get(0), ctx_b.params_get(0))
+    for got, want in zip(ctx_a.adam_get(0), ctx_b.adam_get(0)):
+        np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(ctx_a.ppo_stats(0, pe.shape[1]), ctx_b.ppo_stats(0, pe.shape[1]))
+    ctx_a.close()
+    ctx_b.close()
+
+
 def test_native_ddp_argument_errors(pg1):
     import torch
     from ddrl_amd.native import DdrlError

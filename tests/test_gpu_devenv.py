@@ -387,6 +387,30 @@ def test_eval_table_against_the_host_plane():
     cb.close()
 
 
+def test_eval_table_grows_between_sessions():
+    """ddrl_eval_begin keeps the result table between sessions and replaces it when a session asks for more
+    episodes per env: 1, then 3, on one context (a new env plane of the same seed per session, so both sessions
+    start from the same env state).  The second session's table is, bit for bit, the one a fresh context writes
+    that is run with 3 directly."""
+    n, limit = 16, 4
+    tables = []
+    for sessions in ((1, 3), (3,)):
+        ctx, _ = _eval_ctx(n)
+        for E in sessions:
+            denv = N.DevEnv(ctx, seed=21)
+            denv.set_time_limit(limit)
+            ctx.eval_begin(E, filter_update=False)
+            steps = ctx.eval_devenv(denv, max_steps=2 * E * limit, poll_every=2)
+            table = ctx.eval_results()
+            assert table.shape == (n, E, 6) and 1 < steps <= E * limit and ctx.eval_progress() == (n * E, n)
+            assert not np.isnan(table[:, :, :5]).any()
+            ctx.eval_end()
+            denv.close()
+        tables.append(table)
+        ctx.close()
+    assert_bits(tables[0], tables[1], "result table of the grown session")
+
+
 # ---- messages --------------------------------------------------------------------------------
 def test_refusals_have_messages():
     import torch
