@@ -1,7 +1,7 @@
-// C-ABI of libddrl_hip.so: the two groups of contexts (update, rollout) and the checks every group shares.
+// C-ABI of libddrl_hip.so: the groups of contexts (update, rollout, finish) and the checks every group shares.
 #include "ctx.h"
 
-// ---- what the two groups of contexts (update, rollout) share; `kind` is "update" or "rollout" ----
+// ---- what the groups of contexts (update, rollout, finish) share; `kind` is "update", "rollout" or "finish" ----
 namespace ddrl_impl {
 std::string group_member_name(const char* kind, int m) { return std::string(kind) + " group: member " + std::to_string(m); }
 
@@ -57,6 +57,7 @@ struct ddrl_update_group {
   unsigned epoch = 0;                  // launches so far (granule tag epochs), the group's own
   int inflight = 0;                    // a run is enqueued and not yet finished
   int refused = 0;                     // a placement check failed: no further runs
+  PinnedStage stage;                   // stats_range's copies land here first
 };
 
 namespace {
@@ -112,6 +113,7 @@ int group_same_shape(const ddrl_ctx* a, const ddrl_ctx* b, int m) {
 
 void group_free(ddrl_update_group* g) {
   g->table.release();
+  g->stage.release();
   for (void* p : {(void*)g->xchg, (void*)g->gx, (void*)g->err, (void*)g->xcc})
     if (p) (void)hipFree(p);
   delete g;
@@ -292,6 +294,50 @@ int ddrl_update_group_placement(ddrl_update_group* g, int32_t* xcc, int n_blocks
   return 0;
 }
 
+// ddrl_ppo_stats_range of every chain: the copies are enqueued together and waited for once, with every
+// member's error word behind them; a set word is then handled by that member's own check.
+int ddrl_update_group_stats_range(ddrl_update_group* g, size_t first, size_t n_steps, float* host) {
+  if (!g) return fail("null update group");
+  if (!host && n_steps) return fail("null stats buffer");
+  if (g->inflight) return fail("update group: finish the run before reading its statistics (ddrl_update_group_finish)");
+  const int M = (int)g->members.size(), P = g->P;
+  for (int m = 0; m < M; ++m)
+    for (int p = 0; p < P; ++p) {
+      const size_t cap = g->members[m]->pol[p].stats_steps;
+      if (first > cap || n_steps > cap - first)
+        return fail(member_name(m) + ", policy " + std::to_string(p) + ": more stats requested than the schedule holds");
+    }
+  HIPCHK(hipSetDevice(g->device));
+  // pinned staging: [M][P][n_steps][8] floats, then the members' error words
+  const size_t rows_bytes = (size_t)M * P * n_steps * 8 * sizeof(float);
+  if (g->stage.fit(rows_bytes + sizeof(int) * M)) return -1;
+  float* rows = (float*)g->stage.p;
+  int* errs = (int*)(g->stage.p + rows_bytes);
+  for (int m = 0; m < M; ++m) {
+    const ddrl_ctx* c = g->members[m];
+    for (int p = 0; p < P && n_steps; ++p)
+      HIPCHK(hipMemcpyAsync(rows + ((size_t)m * P + p) * n_steps * 8, c->pol[p].stats + first * 8, n_steps * 8 * 4,
+                            hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(&errs[m], c->err, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+  }
+  HIPCHK(hipStreamSynchronize(g->stream));
+  for (int m = 0; m < M; ++m)
+    if (errs[m] && check_err(g->members[m])) return -1;
+  if (rows_bytes) std::memcpy(host, rows, rows_bytes);
+  // total_loss, as ddrl_ppo_stats_range forms it: mean(-surr) + beta*mean(kl) + vf_coeff*mean(vf) - ent_coeff*mean(H)
+  for (int m = 0; m < M; ++m) {
+    const ddrl_ctx* c = g->members[m];
+    for (int p = 0; p < P; ++p) {
+      const float beta = c->kl_last[p];
+      for (size_t k = 0; k < n_steps; ++k) {
+        float* s = host + (((size_t)m * P + p) * n_steps + k) * 8;
+        s[0] = s[1] + beta * s[3] + c->cfg.vf_loss_coeff * s[2] - c->cfg.entropy_coeff * s[4];
+      }
+    }
+  }
+  return 0;
+}
+
 int ddrl_update_group_destroy(ddrl_update_group* g) {
   if (!g) return 0;
   (void)hipSetDevice(g->device);
@@ -348,7 +394,6 @@ int rgroup_same_shape(ddrl_ctx* a, ddrl_ctx* b, int m) {
   }
   return group_same_result("rollout", m, why);
 }
-#undef DDRL_GRP_SAME
 
 // what a member and its env must still be at every run (create checks it too)
 int rgroup_member_ok(const ddrl_rollout_group* g, int m) {
@@ -460,6 +505,195 @@ int ddrl_rollout_group_destroy(ddrl_rollout_group* g) {
   (void)hipSetDevice(g->device);
   (void)hipStreamSynchronize(g->stream);
   rgroup_free(g);   // (the members may be gone already: they are not touched)
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- group finish (finish_group.hip): GAE and the episode accounting of M same-shaped contexts as one chain ----
+// Member m is the context members[m]: whatever holds its fragment (the synthetic, host or device env
+// plane), the finish reads the records only.  The FinishMember table is rebuilt at every run from the
+// members' current state, so buffers replaced between runs (the episode table's growth) hold.
+struct ddrl_finish_group {
+  std::vector<ddrl_ctx*> members;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  MemberTable<FinishMember> table;
+  long long *totals = nullptr, *totals_host = nullptr;   // [M] device, [M] pinned
+  PinnedStage stage;                                     // rows' copies land here first
+};
+
+namespace {
+std::string fmember_name(int m) { return group_member_name("finish", m); }
+
+// the first difference between member m's configuration and member 0's in anything the finish kernels read
+int fgroup_same_shape(const ddrl_ctx* a, const ddrl_ctx* b, int m) {
+  const ddrl_cfg &x = a->cfg, &y = b->cfg;
+  const char* why = nullptr;
+  DDRL_GRP_SAME(n_envs); DDRL_GRP_SAME(frag_len); DDRL_GRP_SAME(n_agents); DDRL_GRP_SAME(n_policies);
+  for (int j = 0; j < x.n_agents && !why; ++j)
+    if (x.agent_policy[j] != y.agent_policy[j]) why = "agent_policy";
+  for (int p = 0; p < x.n_policies && !why; ++p) {
+    const Policy &P = a->pol[p], &Q = b->pol[p];
+    if (P.k != Q.k || std::memcmp(P.agents, Q.agents, sizeof(P.agents)) != 0) why = "agent_policy";
+    else if (std::memcmp(&P.lay, &Q.lay, sizeof(RecLayout)) != 0) why = "the record layout";
+  }
+  DDRL_GRP_SAME(gamma); DDRL_GRP_SAME(lambda_);
+  return group_same_result("finish", m, why);
+}
+#undef DDRL_GRP_SAME
+
+int fgroup_member_ok(const ddrl_finish_group* g, int m) {
+  if (g->members[m]->stream != g->stream) return fail(fmember_name(m) + " is on another stream than member 0");
+  return 0;
+}
+
+void fgroup_free(ddrl_finish_group* g) {
+  g->table.release();
+  g->stage.release();
+  if (g->totals) (void)hipFree(g->totals);
+  if (g->totals_host) (void)hipHostFree(g->totals_host);
+  delete g;
+}
+}  // namespace
+
+extern "C" {
+
+int ddrl_finish_group_create(ddrl_ctx* const* members, int n_members, ddrl_finish_group** out) {
+  if (!members || !out) return fail("null argument");
+  if (n_members < 1) return fail("finish group: at least one member is needed");
+  if (n_members > 65535)
+    return fail("finish group: " + std::to_string(n_members) + " members exceed the grid's z extent (65535)");
+  if (group_list_ok("finish", members, nullptr, n_members)) return -1;
+  ddrl_ctx* c0 = members[0];
+  HIPCHK(hipSetDevice(c0->device));
+  ddrl_finish_group* g = new ddrl_finish_group();
+  g->members.assign(members, members + n_members);
+  g->device = c0->device;
+  g->stream = c0->stream;
+  int rc = 0;
+  for (int m = 0; m < n_members && !rc; ++m) {
+    if (members[m]->device != g->device) rc = fail(fmember_name(m) + " is on another device than member 0");
+    else rc = fgroup_member_ok(g, m) || fgroup_same_shape(members[m], c0, m);
+  }
+  if (!rc && (!g->table.alloc(n_members) || dev_zalloc((void**)&g->totals, sizeof(long long) * n_members) != hipSuccess ||
+              hipHostMalloc((void**)&g->totals_host, sizeof(long long) * n_members, hipHostMallocDefault) != hipSuccess ||
+              hipDeviceSynchronize() != hipSuccess))
+    rc = fail("finish group: allocation of the member table failed");
+  if (rc) {
+    fgroup_free(g);
+    return -1;
+  }
+  *out = g;
+  return 0;
+}
+
+int ddrl_finish_group_run(ddrl_finish_group* g, int64_t* n_finished) {
+  if (!g) return fail("null finish group");
+  if (!n_finished) return fail("finish group: null count output");
+  const int M = (int)g->members.size();
+  // refusals first: nothing is launched, no member is left half finished
+  for (int m = 0; m < M; ++m) {
+    if (fgroup_member_ok(g, m)) return -1;
+    if (g->members[m]->ep_collected)
+      return fail(fmember_name(m) + ": this fragment has been collected (collect once per fragment, after its last "
+                  "reward); nothing ran on any member");
+  }
+  HIPCHK(hipSetDevice(g->device));
+  for (ddrl_ctx* c : g->members)
+    if (ep_state(c)) return -1;
+  ddrl_ctx* c0 = g->members[0];
+  const ddrl_cfg& cfg = c0->cfg;
+  FinishMember* table = nullptr;
+  if (g->table.host(table)) return -1;
+  for (int m = 0; m < M; ++m) {
+    ddrl_ctx* c = g->members[m];
+    FinishMember& f = table[m];
+    f = FinishMember{};
+    for (int p = 0; p < cfg.n_policies; ++p) {
+      Policy& P = c->pol[p];
+      f.rec[p] = P.rec; f.last_v[p] = P.last_v; f.partials[p] = P.partials; f.adv_norm[p] = P.adv_norm;
+    }
+    f.done_tn = c->done_tn;
+    f.ep_cnt = c->ep_cnt; f.ep_base = c->ep_base; f.ep_word = c->ep_word;
+    f.ep_total = c->ep_total; f.ep_agent = c->ep_agent; f.ep_len = c->ep_len;
+    f.ep_table = c->ep_table; f.ep_cap = c->ep_cap;
+  }
+  if (g->table.upload(g->stream, M)) return -1;
+  FinishGroupArgs fa{};
+  fa.tab = g->table.dev; fa.totals = g->totals;
+  fa.M = M; fa.P = cfg.n_policies; fa.T = cfg.frag_len; fa.N = cfg.n_envs; fa.W = (cfg.n_envs + 63) / 64;
+  fa.n_agents = cfg.n_agents;
+  fa.gamma = cfg.gamma; fa.lambda_ = cfg.lambda_;
+  const RewardArgs ra = make_reward(c0);   // the agent -> policy / slot maps, as ddrl_episodes_collect takes them
+  for (int p = 0; p < cfg.n_policies; ++p) {
+    fa.k[p] = c0->pol[p].k; fa.C[p] = c0->pol[p].C; fa.lay[p] = c0->pol[p].lay;
+  }
+  for (int j = 0; j < cfg.n_agents; ++j) {
+    fa.policy_of_agent[j] = ra.policy_of_agent[j];
+    fa.slot_of_agent[j] = ra.slot_of_agent[j];
+  }
+  launch_finish_group_gae(g->stream, fa);
+  launch_finish_group_count_scan(g->stream, fa);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(g->totals_host, g->totals, sizeof(long long) * M, hipMemcpyDeviceToHost, g->stream));
+  HIPCHK(hipStreamSynchronize(g->stream));   // the one synchronize of the group: nothing in flight reads a table either
+  g->table.stream_synced();
+  for (int m = 0; m < M; ++m) {
+    ddrl_ctx* c = g->members[m];
+    if (ep_table_fit(c, g->totals_host[m])) return -1;
+    table[m].ep_table = c->ep_table;
+    table[m].ep_cap = c->ep_cap;
+  }
+  if (g->table.upload(g->stream, M)) return -1;
+  launch_finish_group_walk(g->stream, fa);
+  HIPCHK(hipGetLastError());
+  for (int m = 0; m < M; ++m) {
+    ddrl_ctx* c = g->members[m];
+    c->ep_collected = 1;
+    c->ep_rows = g->totals_host[m];
+    n_finished[m] = (int64_t)g->totals_host[m];
+  }
+  return 0;
+}
+
+int ddrl_finish_group_rows(ddrl_finish_group* g, double* const* host, const int64_t* n_rows) {
+  if (!g) return fail("null finish group");
+  if (!host || !n_rows) return fail("finish group: null rows argument");
+  const int M = (int)g->members.size();
+  for (int m = 0; m < M; ++m) {
+    const ddrl_ctx* c = g->members[m];
+    if (fgroup_member_ok(g, m)) return -1;
+    if (c->ep_rows < 0) return fail(fmember_name(m) + ": run the group (or ddrl_episodes_collect) first");
+    if (n_rows[m] != (int64_t)c->ep_rows) return fail(fmember_name(m) + ": n_rows differs from the last collect's count");
+    if (n_rows[m] && !host[m]) return fail(fmember_name(m) + ": null rows buffer");
+  }
+  HIPCHK(hipSetDevice(g->device));
+  // every member's rows into the pinned staging, one synchronize, then out to the caller's arrays
+  size_t total = 0;
+  for (int m = 0; m < M; ++m) total += (size_t)n_rows[m] * 8 * sizeof(double);
+  if (g->stage.fit(total)) return -1;
+  size_t off = 0;
+  for (int m = 0; m < M; ++m) {
+    const size_t bytes = (size_t)n_rows[m] * 8 * sizeof(double);
+    if (bytes) HIPCHK(hipMemcpyAsync(g->stage.p + off, g->members[m]->ep_table, bytes, hipMemcpyDeviceToHost, g->stream));
+    off += bytes;
+  }
+  HIPCHK(hipStreamSynchronize(g->stream));
+  off = 0;
+  for (int m = 0; m < M; ++m) {
+    const size_t bytes = (size_t)n_rows[m] * 8 * sizeof(double);
+    if (bytes) std::memcpy(host[m], g->stage.p + off, bytes);
+    off += bytes;
+  }
+  return 0;
+}
+
+int ddrl_finish_group_destroy(ddrl_finish_group* g) {
+  if (!g) return 0;
+  (void)hipSetDevice(g->device);
+  (void)hipStreamSynchronize(g->stream);
+  fgroup_free(g);   // (the members may be gone already: they are not touched)
   return 0;
 }
 

@@ -304,12 +304,34 @@ int ddrl_rollout_hostenv(ddrl_ctx* c, ddrl_hostenv* env, int groups, const float
 
 // ---- episode accounting of the training rollout (episodes.hip) ---------------------------
 // Nothing here writes a record, done_tn, last_v, a filter, Adam state or a parameter.
-static int ep_state(ddrl_ctx* c) {
+}  // extern "C"
+
+namespace ddrl_impl {
+int ep_state(ddrl_ctx* c) {
   if (c->ep_total) return 0;
   const size_t N = c->cfg.n_envs, TW = (size_t)c->cfg.frag_len * ((N + 63) / 64);
   return dalloc(c, &c->ep_total, N) || dalloc(c, &c->ep_agent, N * DDRL_MAXAG) || dalloc(c, &c->ep_len, N) ||
          dalloc(c, &c->ep_cnt, TW) || dalloc(c, &c->ep_base, TW) || dalloc(c, &c->ep_word, 1);
 }
+
+// The table of a collect that counted `total` episodes: the count is checked against the fragment's
+// size and the table grown to max(total, 2 * cap) rows when it holds fewer.  The caller has
+// synchronized the stream, so nothing in flight reads the old table.
+int ep_table_fit(ddrl_ctx* c, long long total) {
+  if (total < 0 || total > (long long)c->cfg.frag_len * c->cfg.n_envs) return fail("episodes: bad episode count");
+  if (total > c->ep_cap) {
+    const long long cap = std::max(total, 2 * c->ep_cap);
+    dfree(c, &c->ep_table);
+    c->ep_cap = 0;
+    c->ep_rows = -1;
+    if (dalloc(c, &c->ep_table, (size_t)cap * 8)) return -1;
+    c->ep_cap = cap;
+  }
+  return 0;
+}
+}  // namespace ddrl_impl
+
+extern "C" {
 
 int ddrl_episodes_collect(ddrl_ctx* c, int64_t* n_finished) {
   CHK_CTX(c);
@@ -333,15 +355,7 @@ int ddrl_episodes_collect(ddrl_ctx* c, int64_t* n_finished) {
   long long total = 0;
   HIPCHK(hipMemcpyAsync(&total, c->ep_word, sizeof(total), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));   // the one synchronize: nothing in flight reads the table either
-  if (total < 0 || total > (long long)g.frag_len * g.n_envs) return fail("episodes: bad episode count");
-  if (total > c->ep_cap) {
-    const long long cap = std::max(total, 2 * c->ep_cap);
-    dfree(c, &c->ep_table);
-    c->ep_cap = 0;
-    c->ep_rows = -1;
-    if (dalloc(c, &c->ep_table, (size_t)cap * 8)) return -1;
-    c->ep_cap = cap;
-  }
+  if (ep_table_fit(c, total)) return -1;
   a.table = c->ep_table; a.cap = c->ep_cap;
   launch_ep_walk(c->stream, a);
   HIPCHK(hipGetLastError());

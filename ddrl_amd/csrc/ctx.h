@@ -103,6 +103,29 @@ struct MemberTable {
   }
 };
 
+// A group's pinned staging buffer of device-to-host copies: many copies are enqueued into it, waited for once and
+// handed to the caller's (pageable) arrays by the host.  fit() keeps the old contents of nothing: call it before the
+// copies, with nothing in flight into the buffer.
+struct PinnedStage {
+  char* p = nullptr;
+  size_t cap = 0;
+  int fit(size_t bytes) {
+    if (bytes <= cap) return 0;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    const size_t want = std::max(bytes, 2 * cap);
+    cap = 0;
+    HIPCHK(hipHostMalloc((void**)&p, want, hipHostMallocDefault));
+    cap = want;
+    return 0;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
 // the member tables of the group fills a context led (device randomness, capi_rng.cpp)
 struct RngTables {
   MemberTable<NoiseMember> noise;
@@ -310,6 +333,8 @@ int check_err(ddrl_ctx* c);
 RewardArgs make_reward(ddrl_ctx* c);
 int graph_run(ddrl_ctx* c, hipGraphExec_t* exec, bool stale, const std::function<int()>& launches);
 void rollout_ran(ddrl_ctx* c);
+int ep_state(ddrl_ctx* c);                        // the episode accounting's buffers, allocated on first use
+int ep_table_fit(ddrl_ctx* c, long long total);   // count check + table growth of a collect
 // capi_devenv.cpp
 int chk_env_of(const ddrl_ctx* c, const ddrl_devenv* e);
 // capi_update.cpp

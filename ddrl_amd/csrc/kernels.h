@@ -228,6 +228,33 @@ struct EpArgs {
 void launch_ep_count_scan(hipStream_t s, const EpArgs& a);   // cnt, base, total
 void launch_ep_walk(hipStream_t s, const EpArgs& a);         // table rows + the in-flight state
 
+// ---- group finish (finish_group.hip): GAE and the episode accounting of M contexts side by side ----
+// The kernels of launch_gae, launch_ep_count_scan and launch_ep_walk with the member in blockIdx.z.
+// What differs between members is one FinishMember in a device table; what is equal for all
+// (sizes, record layouts, gamma / lambda, the agent maps) goes by value.
+struct FinishMember {
+  float* rec[DDRL_MAXP];
+  const float* last_v[DDRL_MAXP];
+  double* partials[DDRL_MAXP];     // GaeArgs::partials of each policy
+  float* adv_norm[DDRL_MAXP];
+  const uint8_t* done_tn;
+  int* ep_cnt; long long* ep_base; long long* ep_word;
+  double* ep_total; double* ep_agent; int* ep_len;
+  double* ep_table; long long ep_cap;
+};
+struct FinishGroupArgs {
+  const FinishMember* tab;         // device table of M members
+  long long* totals;               // [M] episodes finished per member (the scan writes it)
+  int M, P, T, N, W, n_agents;     // W = ceil(N / 64)
+  int k[DDRL_MAXP], C[DDRL_MAXP];
+  RecLayout lay[DDRL_MAXP];
+  double gamma, lambda_;
+  int policy_of_agent[DDRL_MAXAG], slot_of_agent[DDRL_MAXAG];
+};
+void launch_finish_group_gae(hipStream_t s, const FinishGroupArgs& fa);          // k_gae + finalize
+void launch_finish_group_count_scan(hipStream_t s, const FinishGroupArgs& fa);   // cnt, base, totals
+void launch_finish_group_walk(hipStream_t s, const FinishGroupArgs& fa);         // table rows + in-flight state
+
 // ---- device env plane (devenv.hip; the dynamics are envdyn.h's) ----
 // The env state is a struct of arrays: st[f][N], f = the first 38 entries of the packed layout
 // (torso 10, q 8, qd 8, qfrc 8, foot 4) and the target velocity as field 38; steps and episode

@@ -48,34 +48,46 @@ class EpisodeHistory:
     def summarize(self, rows, agent_policy, policy_ids):
         """rows: [n, 8] in (t, env) order; agent_policy: policy index of every agent;
         policy_ids: the policies' names.  Returns the EPISODE_KEYS dict."""
-        new = self._episodes(rows, agent_policy)
-        episodes = list(new)
-        missing = max(0, self.smoothing - len(episodes))
-        if missing > 0:
-            episodes = self.history[-missing:] + episodes
-        self.history.extend(new)
-        self.history = self.history[-self.smoothing:] if self.smoothing > 0 else []
+        # Array operations over the columns: the cost in Python does not grow with the row count (a
+        # fragment of 4096 envs finishes thousands of episodes).  Only the kept history -- at most
+        # `smoothing` episodes -- is ever held row by row.  The window's values and their order are
+        # the per-row walk's, so np.min / np.max / np.mean see the same numbers in the same order.
+        rows = np.asarray(rows, np.float64).reshape(-1, 8)
+        agent_policy = [int(p) for p in agent_policy]
+        n = rows.shape[0]
+        missing = max(0, self.smoothing - n)
+        old = self.history[-missing:] if missing > 0 else []
+        keep = self._episodes(rows[n - min(n, self.smoothing):], agent_policy) if self.smoothing > 0 else []
+        self.history = (self.history + keep)[-self.smoothing:] if self.smoothing > 0 else []
 
-        rewards = [ep[0] for ep in episodes]
-        lengths = [ep[1] for ep in episodes]
-        policy_rewards = {}
-        for ep in episodes:
-            for p, r in ep[2]:
-                policy_rewards.setdefault(policy_ids[p], []).append(r)
+        def window(old_values, new_values, dtype):
+            """(array, list) of the kept episodes' values followed by the new ones."""
+            new_values = np.ascontiguousarray(new_values, dtype)
+            if not old_values:
+                return new_values, new_values.tolist()
+            return np.concatenate([np.array(old_values, dtype), new_values]), old_values + new_values.tolist()
+
+        r_arr, rewards = window([ep[0] for ep in old], rows[:, 3], np.float64)
+        l_arr, lengths = window([ep[1] for ep in old], rows[:, 2].astype(np.int64), np.int64)
         nan = float("nan")
         hist = {"episode_reward": rewards, "episode_lengths": lengths}
         pmin, pmax, pmean = {}, {}, {}
-        for pid, rs in policy_rewards.items():
-            pmin[pid] = float(np.min(rs))
-            pmax[pid] = float(np.max(rs))
-            pmean[pid] = float(np.mean(rs))
-            hist[f"policy_{pid}_reward"] = rs
+        if rewards:
+            # one entry per (agent, policy) pair per episode; the policies in the order of their first agent
+            for p in dict.fromkeys(agent_policy):
+                cols = [4 + j for j, q in enumerate(agent_policy) if q == p]
+                a, rs = window([r for ep in old for q, r in ep[2] if q == p], rows[:, cols].ravel(), np.float64)
+                pid = policy_ids[p]
+                pmin[pid] = float(np.min(a))
+                pmax[pid] = float(np.max(a))
+                pmean[pid] = float(np.mean(a))
+                hist[f"policy_{pid}_reward"] = rs
         return {
-            "episode_reward_max": float(np.max(rewards)) if rewards else nan,
-            "episode_reward_min": float(np.min(rewards)) if rewards else nan,
-            "episode_reward_mean": float(np.mean(rewards)) if rewards else nan,
-            "episode_len_mean": float(np.mean(lengths)) if lengths else nan,
-            "episodes_this_iter": len(new),
+            "episode_reward_max": float(np.max(r_arr)) if rewards else nan,
+            "episode_reward_min": float(np.min(r_arr)) if rewards else nan,
+            "episode_reward_mean": float(np.mean(r_arr)) if rewards else nan,
+            "episode_len_mean": float(np.mean(l_arr)) if lengths else nan,
+            "episodes_this_iter": n,
             "policy_reward_min": pmin,
             "policy_reward_max": pmax,
             "policy_reward_mean": pmean,

@@ -182,6 +182,11 @@ _SIGS = {
     "ddrl_update_group_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32)], C.c_int),
     "ddrl_update_group_placement": ([VP, C.POINTER(i32), C.c_int], C.c_int),
     "ddrl_update_group_destroy": ([VP], C.c_int),
+    "ddrl_update_group_stats_range": ([VP, C.c_size_t, C.c_size_t, VP], C.c_int),
+    "ddrl_finish_group_create": ([C.POINTER(VP), C.c_int, C.POINTER(VP)], C.c_int),
+    "ddrl_finish_group_run": ([VP, C.POINTER(C.c_int64)], C.c_int),
+    "ddrl_finish_group_rows": ([VP, C.POINTER(VP), C.POINTER(C.c_int64)], C.c_int),
+    "ddrl_finish_group_destroy": ([VP], C.c_int),
     "ddrl_rollout_group_create": ([C.POINTER(VP), C.POINTER(VP), C.c_int, C.POINTER(VP)], C.c_int),
     "ddrl_rollout_group_run": ([VP, C.POINTER(VP), C.c_int], C.c_int),
     "ddrl_rollout_group_destroy": ([VP], C.c_int),
@@ -805,6 +810,13 @@ class UpdateGroup:
         finally:
             self._keep = None
 
+    def stats_range(self, first, n_steps):
+        """Context.ppo_stats(p, n_steps, first) of every member and policy after a finished run,
+        float32 [M, P, n_steps, 8], with one synchronize for the group."""
+        a = np.empty((len(self.contexts), self.P, int(n_steps), 8), np.float32)
+        _ck(self.lib.ddrl_update_group_stats_range(self._h(), int(first), int(n_steps), a.ctypes.data))
+        return a
+
     def placement(self):
         """XCC id of every block of the last finished run: the launches' grids in launch order, one flat
         array (update_group_plan and update_group_grid give each launch's share)."""
@@ -857,6 +869,42 @@ class RolloutGroup:
     def close(self):
         if getattr(self, "h", None):
             self.lib.ddrl_rollout_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FinishGroup:
+    """Context.gae + Context.episodes_collect of several same-shaped contexts as one chain of launches
+    (a ddrl_finish_group), every member left bit-identical to its own calls.  Any env plane and model
+    kind: only the records are read.  Close the group before its members."""
+
+    def __init__(self, contexts):
+        self.lib = load()
+        self.contexts = list(contexts)
+        n = len(self.contexts)
+        h = VP()
+        _ck(self.lib.ddrl_finish_group_create((VP * max(1, n))(*[c.h for c in self.contexts]), n, C.byref(h)))
+        self.h = h
+
+    def run(self):
+        """One float64 [n_m, 8] array of episode rows (EPISODE_COLUMNS) per member; synchronizes."""
+        if not getattr(self, "h", None):
+            raise DdrlError("finish group: used after close")
+        n = len(self.contexts)
+        counts = (C.c_int64 * n)()
+        _ck(self.lib.ddrl_finish_group_run(self.h, counts))
+        rows = [np.empty((int(k), 8), np.float64) for k in counts]
+        _ck(self.lib.ddrl_finish_group_rows(self.h, (VP * n)(*[a.ctypes.data for a in rows]), counts))
+        return rows
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ddrl_finish_group_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -7,8 +7,11 @@ m of a PopulationTrainer is, bit for bit, the solo PPOTrainer(config, seed=seeds
 context, envs, noise, schedule, filters, KL coefficients and results -- with the M update launches
 of an iteration replaced by one.  On the device env plane the members' fragments are one chain of
 launches too (native.RolloutGroup, csrc/rollout_group.hip), each member drawing its noise from its
-own generator as the solo trainer does; GAE and the episode accounting stay per member.  On the
-synthetic and host planes sampling stays per member, in stream order.  With rng_backend "device"
+own generator as the solo trainer does.  On the synthetic and host planes sampling stays per member,
+in stream order.  What follows a fragment -- GAE and the episode accounting -- is one chain for all
+members on every plane (native.FinishGroup, csrc/finish_group.hip: it reads the records only), with
+one host synchronize per population, and the learner statistics of an iteration are read in one call
+(UpdateGroup.stats_range).  With rng_backend "device"
 every member's generator is its context's pair of device streams, and the members' noise slabs
 and schedules are one group launch each (native.noise_fill_group, native.schedule_fill_group)
 instead of host draws member by member.
@@ -32,9 +35,12 @@ class PopulationTrainer:
     group_rollout: None = the members' fragments as one group chain when every member runs the device
     env plane (env_backend "device"), member by member otherwise; True = the group chain, or an error
     with the reason; False = member by member.  The results are the same bit for bit.
+    group_finish: None / True = GAE and the episode accounting of all members as one group chain, on
+    every env plane; False = member by member.  The results are the same bit for bit.
     """
 
-    def __init__(self, config, seeds, n_envs=None, device=0, max_chains_per_launch=0, group_rollout=None):
+    def __init__(self, config, seeds, n_envs=None, device=0, max_chains_per_launch=0, group_rollout=None,
+                 group_finish=None):
         import torch
         self.torch = torch
         self.seeds = [int(s) for s in seeds]
@@ -44,6 +50,7 @@ class PopulationTrainer:
         self.trainers = []
         self.group = None
         self.rollout_group = None
+        self.finish_group = None
         try:
             for s in self.seeds:
                 self.trainers.append(PPOTrainer(config, n_envs=n_envs, device=device, seed=s, stream=self.stream))
@@ -55,6 +62,8 @@ class PopulationTrainer:
             self.device_rng = bool(self.trainers) and self.trainers[0].rng_backend == "device"
             self.group = N.UpdateGroup([t.ctx for t in self.trainers], max_chains_per_launch)
             self._init_group_rollout(group_rollout)
+            if group_finish is None or group_finish:
+                self.finish_group = N.FinishGroup([t.rctx for t in self.trainers])
         except Exception:
             self.stop()
             raise
@@ -91,8 +100,24 @@ class PopulationTrainer:
                 for step in range(t.T):
                     torch.randn(tuple(slab.shape[1:]), generator=t.noise_gen, out=slab[step])
         self.rollout_group.run(self.noise)
-        for t in self.trainers:
-            t._sample_finish()
+
+    def _finish(self):
+        """What follows the members' fragments: one group chain, or every member's own calls."""
+        if self.finish_group is None:
+            for t in self.trainers:
+                t._sample_finish()
+            return
+        # (a population's members are single-process replicas: _sample_finish has no cross-rank part)
+        for t, rows in zip(self.trainers, self.finish_group.run()):
+            t._episode_rows = rows
+
+    def _learn_stats(self, nbs):
+        """Every member's last-epoch statistics rows ([M] lists of [P] arrays) in one readback, or None
+        where the policies' schedules differ in length (the members then read their own)."""
+        if len(set(nbs)) != 1:
+            return None
+        a = self.group.stats_range((self.trainers[0].cfg.num_sgd_iter - 1) * nbs[0], nbs[0])
+        return [list(a[m]) for m in range(len(self.trainers))]
 
     def train(self):
         """One iteration of every member; the list of the members' result dicts."""
@@ -101,7 +126,8 @@ class PopulationTrainer:
             self._sample_group()
         else:
             for t in self.trainers:
-                t._sample()
+                t._sample_fragment()
+        self._finish()
         self.torch.cuda.synchronize(self.device)
         t1 = time.perf_counter()
         if self.device_rng:   # every member's schedule in one launch, into its own persistent arrays
@@ -110,7 +136,9 @@ class PopulationTrainer:
         sched = [t._learn_schedules(fill=False) for t in self.trainers]
         self.group.run([s[0] for s in sched], [s[1] for s in sched], [t.kl_coeff for t in self.trainers])
         self.group.finish()
-        learners = [t._learn_results(s[2]) for t, s in zip(self.trainers, sched)]
+        stats = self._learn_stats(sched[0][2]) if sched else None
+        learners = [t._learn_results(s[2], stats[m] if stats else None)
+                    for m, (t, s) in enumerate(zip(self.trainers, sched))]
         t2 = time.perf_counter()
         return [t._iteration_result(lr, t0, t1, t2) for t, lr in zip(self.trainers, learners)]
 
@@ -128,6 +156,9 @@ class PopulationTrainer:
             self.rollout_group.close()
             self.rollout_group = None
         self.noise = []
+        if getattr(self, "finish_group", None) is not None:   # before its members
+            self.finish_group.close()
+            self.finish_group = None
         if self.group is not None:   # before its members
             self.group.close()
             self.group = None

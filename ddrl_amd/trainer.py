@@ -356,14 +356,21 @@ class PPOTrainer:
             nbs.append(nb)
         return sh, pe, nbs
 
-    def _learn_results(self, nbs):
+    def _last_epoch_stats(self, nbs):
+        """The last epoch's statistics rows of every policy, float32 [nbs[p], 8] each."""
+        return [self.ctx.ppo_stats(p, nbs[p], first=(self.cfg.num_sgd_iter - 1) * nbs[p])
+                for p in range(self.cfg.n_policies)]
+
+    def _learn_results(self, nbs, stats=None):
         """The part after the launch (this trainer's own, or a group's: ddrl_amd.population): the last
-        epoch's statistics, update_kl and the learner dict."""
+        epoch's statistics, update_kl and the learner dict.  stats: the rows of _last_epoch_stats when
+        the caller has read them already (a population reads all members' in one call)."""
         P = self.cfg.n_policies
+        if stats is None:
+            stats = self._last_epoch_stats(nbs)
         learner = {}
         for p, pid in enumerate(self.policy_ids):
-            st = self.ctx.ppo_stats(p, nbs[p], first=(self.cfg.num_sgd_iter - 1) * nbs[p])
-            last = st.astype(np.float64).mean(0)   # TrainTFMultiGPU: last epoch's mean
+            last = stats[p].astype(np.float64).mean(0)   # TrainTFMultiGPU: last epoch's mean
             learner[pid] = {"cur_kl_coeff": float(np.float32(self.kl_coeff[p])),
                             "cur_lr": float(np.float32(self.cfg.lr)),
                             "total_loss": last[0], "policy_loss": last[1], "vf_loss": last[2],

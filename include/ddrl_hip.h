@@ -508,6 +508,11 @@ int ddrl_update_group_plan(int n_members, int n_policies, int max_chains, int32_
                            int32_t* first_block_of_chain);
 int ddrl_update_group_placement(ddrl_update_group* group, int32_t* xcc, int n_blocks);
 int ddrl_update_group_destroy(ddrl_update_group* group);
+/* stats_range: ddrl_ppo_stats_range(first, n_steps) of every policy of every member after a finished
+ * run, host[n_members][n_policies][n_steps][8]: every copy is enqueued, then one synchronize.  The
+ * per-context call's refusals (a null buffer, a range past the schedule's rows, a set error word),
+ * and a run that has not been finished. */
+int ddrl_update_group_stats_range(ddrl_update_group* group, size_t first, size_t n_steps, float* host);
 
 /* Group rollout (rollout_group.hip): the device-plane fragments of n_members same-shaped contexts
  * as ONE in-order chain of launches, the member in the grid's z.  Member m is the context
@@ -538,6 +543,34 @@ int ddrl_rollout_group_create(ddrl_ctx* const* members, ddrl_devenv* const* envs
                               ddrl_rollout_group** out);
 int ddrl_rollout_group_run(ddrl_rollout_group* group, const float* const* eps_dev, int reset);
 int ddrl_rollout_group_destroy(ddrl_rollout_group* group);
+
+/* Group finish (finish_group.hip): what lies between a fragment's last env step and the update --
+ * ddrl_gae and ddrl_episodes_collect -- for n_members same-shaped contexts as ONE in-order chain of
+ * launches, the member in the grid's z, with one host synchronize for the group where the plain
+ * calls have one per member.  Only the records are read, so the fragment may come from any env
+ * plane and any model kind (GraphNet included).  Every member stays a full, ordinary context and
+ * is left, bit for bit, as ddrl_gae + ddrl_episodes_collect leave it (adv / vt columns, adv_norm,
+ * the GAE totals, the episode table, the in-flight state and the host-side notes), so
+ * ddrl_episodes_rows, ddrl_episodes_inflight, ddrl_adv_sums_get, ddrl_adv_norm_get, the "collected
+ * once" refusal and a following update (solo or group) behave unchanged.
+ *   create: members[n_members] (at most 65535), all on one device and one stream (the group
+ *     enqueues on it).  Refuses, naming the member and the reason: no member, a null or repeated
+ *     context, another device or stream, and "finish group: member m differs from member 0 in
+ *     <field>" for the first of n_envs, frag_len, n_agents, n_policies, agent_policy, the record
+ *     layout, gamma, lambda_ that differs.  The group owns the member table (device, filled from a
+ *     pinned host buffer) and the totals array.  Destroy the group before its members.
+ *   run: the GAE scan and its finalize, the episode count and scan, one copy of the members' totals
+ *     and the synchronize, the plain collect's count check and table growth (max(total, 2 * cap))
+ *     per member on the host, the walk.  n_finished[n_members]: rows per member.  The member table
+ *     is rebuilt at every run from the members' current state.  If any member has been collected
+ *     this fragment, the whole run is refused before anything is launched.
+ *   rows: ddrl_episodes_rows of every member, host[m] holding n_rows[m] rows of 8 doubles, with one
+ *     synchronize; refuses an n_rows[m] that differs from member m's last count. */
+typedef struct ddrl_finish_group ddrl_finish_group;
+int ddrl_finish_group_create(ddrl_ctx* const* members, int n_members, ddrl_finish_group** out);
+int ddrl_finish_group_run(ddrl_finish_group* group, int64_t* n_finished);
+int ddrl_finish_group_rows(ddrl_finish_group* group, double* const* host, const int64_t* n_rows);
+int ddrl_finish_group_destroy(ddrl_finish_group* group);
 
 /* Device randomness (rng.hip): the exploration noise of a fragment and the minibatch schedules of an
  * update drawn on the device by a counter-based generator, Philox4x32-10 (csrc/philox.h; the exact

@@ -22,6 +22,14 @@ and whether the group beat the replays in every run by more than the replays' ow
     draws they replace (M x T torch.randn calls; M x P numpy schedules and their uploads); and, with
     --parent-root, the host backend's iterations on this tree and on the parent's, child processes,
     alternating.
+  --finish: instead of the above, the group finish ("Population finish"; default
+    output profiles/population/finish_time.json), rng_backend "device" throughout.  At the
+    --iterations sizes: PopulationTrainer iterations with group_finish on and off, child processes,
+    alternating, each iteration split by synchronizes into chain / finish / learn / learner-statistics
+    readback / summary, with the episode rows of every member and iteration; the finish alone at
+    M = 1, 4 and 16 (FinishGroup.run against M x (gae + episodes_collect), a fresh fragment in front
+    of every call); and, with --parent-root, whole solo PPOTrainer.train() and default
+    PopulationTrainer.train() iterations on this tree and on the parent's, child processes, alternating.
 Writes one JSON document (default profiles/population/rollout_time.json).
 """
 import argparse
@@ -285,6 +293,184 @@ def main_rng(a):
         json.dump(res, f, indent=1)
 
 
+# ---- --finish: the group finish ("Population finish") ----
+def split_iteration(pop):
+    """One PopulationTrainer.train() with a synchronize between its parts: milliseconds of the rollout
+    chain, the finish, the learn launch, the learner-statistics readback and the host-side results
+    (update_kl and the episode summary), and the episode rows of every member."""
+    import torch
+    from ddrl_amd import native as N
+    marks = [time.perf_counter()]
+
+    def mark():
+        torch.cuda.synchronize()
+        marks.append(time.perf_counter())
+    if pop.rollout_group is not None:
+        pop._sample_group()
+    else:
+        for t in pop.trainers:
+            t._sample_fragment()
+    mark()
+    pop._finish()
+    mark()
+    if pop.device_rng:
+        N.schedule_fill_group([t.ctx for t in pop.trainers], [t.sched[0] for t in pop.trainers],
+                              [t.sched[1] for t in pop.trainers])
+    sched = [t._learn_schedules(fill=False) for t in pop.trainers]
+    pop.group.run([s[0] for s in sched], [s[1] for s in sched], [t.kl_coeff for t in pop.trainers])
+    pop.group.finish()
+    mark()
+    stats = pop._learn_stats(sched[0][2])
+    mark()
+    learners = [t._learn_results(s[2], stats[m] if stats else None) for m, (t, s) in enumerate(zip(pop.trainers, sched))]
+    results = [t._iteration_result(lr, marks[0], marks[1], marks[3]) for t, lr in zip(pop.trainers, learners)]
+    marks.append(time.perf_counter())
+    ms = [(b - a) * 1e3 for a, b in zip(marks, marks[1:])]
+    return {"chain_ms": ms[0], "finish_ms": ms[1], "learn_ms": ms[2], "stats_readback_ms": ms[3], "summary_ms": ms[4],
+            "iteration_ms": sum(ms), "episode_rows": [r["episodes_this_iter"] for r in results]}
+
+
+def finish_child(root, mode, M, n_envs, T, repeats):
+    """Child process on the tree at `root`; one JSON line.  mode: "group" / "members" = the split
+    iterations of a population with group_finish on / off (this tree); "population" = whole
+    PopulationTrainer.train() calls as the tree ships them; "solo" = whole PPOTrainer.train() calls."""
+    sys.path.insert(0, root)
+    config = {"env": LOCAL, "env_backend": "device", "rollout_fragment_length": T, "rng_backend": "device"}
+    runs = []
+    if mode == "solo":
+        from ddrl_amd.trainer import PPOTrainer
+        tr = PPOTrainer(config, n_envs=n_envs, seed=0)
+        for it in range(repeats + 1):
+            t0 = time.perf_counter()
+            r = tr.train()
+            runs.append({"iteration_ms": (time.perf_counter() - t0) * 1e3, "episode_rows": [r["episodes_this_iter"]]})
+        tr.stop()
+    else:
+        from ddrl_amd.population import PopulationTrainer
+        kw = {} if mode == "population" else {"group_finish": mode == "group"}
+        pop = PopulationTrainer(config, range(M), n_envs=n_envs, **kw)
+        for it in range(repeats + 1):
+            if mode == "population":
+                t0 = time.perf_counter()
+                r = pop.train()
+                runs.append({"iteration_ms": (time.perf_counter() - t0) * 1e3, "sample_ms": r[0]["timers"]["sample_time_ms"],
+                             "learn_ms": r[0]["timers"]["learn_time_ms"], "episode_rows": [x["episodes_this_iter"] for x in r]})
+            else:
+                runs.append(split_iteration(pop))
+        pop.stop()
+    print(json.dumps(runs[1:]))   # the first iteration is the warm-up
+
+
+def finish_children(a, root, mode, M, n):
+    return child_json([sys.executable, os.path.abspath(__file__), "--finish-child", root, "--finish-mode", mode,
+                       "--members", str(M), "--envs", str(n), "--frag-len", str(a.frag_len), "--repeats", str(a.repeats)],
+                      root, f"the {mode} child of {root}")
+
+
+def columns(runs):
+    keys = [k for k in runs[0] if k != "episode_rows"]
+    return {**{k: summary([r[k] for r in runs]) for k in keys}, "runs": runs}
+
+
+def time_finish_alone(N, make_cfg, n_envs, T, M, repeats):
+    """The finish alone: FinishGroup.run (rows included) against M x (gae + episodes_collect), wall
+    clock around a synchronized call, a fresh device-plane fragment in front of every call."""
+    members, cfg = make_members(N, make_cfg, LOCAL, n_envs, T, M)
+    ctxs = [x[0] for x in members]
+    group = N.FinishGroup(ctxs)
+    rows = []
+
+    def fragment():
+        for ctx, env_m, gen, slab, actions in members:
+            slab.normal_(generator=gen)
+            ctx.rollout_devenv(env_m, slab)
+
+    def run_group():
+        rows.append([int(r.shape[0]) for r in group.run()])
+
+    def run_members():
+        for ctx in ctxs:
+            ctx.gae()
+            ctx.episodes_collect()
+    variants = {"group": run_group, "members": run_members}
+    ms = {k: [] for k in variants}
+    for it in range(repeats + 1):   # the first round is the warm-up
+        for k, fn in variants.items():
+            fragment()
+            dt = wall(fn)
+            if it:
+                ms[k].append(dt)
+    group.close()
+    for ctx, env_m, *_ in members:
+        env_m.close()
+        ctx.close()
+    spread = max(ms["members"]) - min(ms["members"])
+    res = {"members": M, "envs": n_envs, "frag_len": T, "unit": "milliseconds, wall clock around a synchronized call",
+           "runs": ms, **{f"{k}_ms": summary(v) for k, v in ms.items()},
+           "members_over_group": statistics.median(ms["members"]) / statistics.median(ms["group"]),
+           "members_spread_ms": spread, "episode_rows_per_member": rows,
+           "group_beats_members_every_run_by_more_than_their_spread":
+               bool(all(b - a > spread for a, b in zip(ms["group"], ms["members"])))}
+    print(json.dumps({k: v for k, v in res.items() if k not in ("runs", "episode_rows_per_member")}), flush=True)
+    return res
+
+
+def main_finish(a):
+    if a.finish_child:
+        return finish_child(a.finish_child, a.finish_mode, a.members, a.envs, a.frag_len, a.repeats)
+    sys.path.insert(0, HERE)
+    import torch
+    from ddrl_amd import native as N
+    from ddrl_amd.spec import make_cfg
+    if not torch.cuda.is_available():
+        sys.exit("population_rollout_time: needs a GPU (no timing without one)")
+    out = a.out or os.path.join(HERE, "profiles", "population", "finish_time.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    sizes = [(int(m), int(n)) for m, n in (s.split(":") for s in a.iterations.split(",") if s)]
+    res = {"device": torch.cuda.get_device_name(0), "commit": a.commit, "frag_len": a.frag_len, "repeats": a.repeats,
+           "rounds": a.rounds, "iterations": [], "finish_alone": []}
+
+    def dump():   # after every section: a run that is cut short leaves what it has measured
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+    for M, n in sizes:
+        runs = {"group": [], "members": []}
+        for rnd in range(a.rounds):   # neither variant always follows the other
+            for mode in (("group", "members") if rnd % 2 == 0 else ("members", "group")):
+                runs[mode] += finish_children(a, HERE, mode, M, n)
+        entry = {"members": M, "envs": n, "frag_len": a.frag_len, **{k: columns(v) for k, v in runs.items()}}
+        fm = [r["finish_ms"] for r in runs["members"]]
+        spread = max(fm) - min(fm)
+        gain = statistics.median(fm) - statistics.median([r["finish_ms"] for r in runs["group"]])
+        entry.update({"finish_members_spread_ms": spread, "finish_members_minus_group_ms": gain,
+                      "group_finish_faster_by_more_than_the_members_spread": bool(gain > spread),
+                      "episode_rows_per_member_and_iteration": [r["episode_rows"] for r in runs["group"]]})
+        print(json.dumps({k: v for k, v in entry.items() if k not in ("group", "members", "episode_rows_per_member_and_iteration")}
+                         | {m: {k: v for k, v in entry[m].items() if k != "runs"} for m in ("group", "members")}), flush=True)
+        res["iterations"].append(entry)
+        for alone_m in (1, 4, 16):
+            res["finish_alone"].append(time_finish_alone(N, make_cfg, n, a.frag_len, alone_m, a.repeats))
+        dump()
+    if a.parent_root:
+        trees = (("this", HERE), ("parent", os.path.abspath(a.parent_root)))
+        res["against_parent"] = []
+        for M, n in sizes:
+            for mode in ("solo", "population"):
+                it = {"this": [], "parent": []}
+                rows = {"this": [], "parent": []}
+                for rnd in range(a.rounds):
+                    for name, root in (trees if rnd % 2 == 0 else trees[::-1]):
+                        got = finish_children(a, root, mode, M, n)
+                        it[name] += [r["iteration_ms"] for r in got]
+                        rows[name] += [r["episode_rows"] for r in got]
+                what = "PPOTrainer.train()" if mode == "solo" else f"PopulationTrainer.train() of {M} seeds, defaults"
+                res["against_parent"].append({"mode": mode, "members": 1 if mode == "solo" else M, "envs": n, "episode_rows": rows,
+                                              **against(it, f"milliseconds per {what}, Local, {n} envs x {a.frag_len} steps, "
+                                                            f"rng_backend device; {a.rounds} alternating processes per tree x {a.repeats}")})
+                dump()
+    dump()
+
+
 def solo_child(root, n_envs, T, repeats):
     """Child process: the solo ddrl_rollout_devenv fragment of Local on the tree at `root`; one JSON line."""
     sys.path.insert(0, root)
@@ -346,11 +532,18 @@ def main():
     ap.add_argument("--solo-child", default="", help=argparse.SUPPRESS)
     ap.add_argument("--rng", action="store_true", help="time the device generator (rng_backend host against device)")
     ap.add_argument("--rng-child", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--finish", action="store_true", help="time the group finish (group_finish on against off)")
+    ap.add_argument("--finish-child", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--finish-mode", default="group", help=argparse.SUPPRESS)
+    ap.add_argument("--members", type=int, default=16, help=argparse.SUPPRESS)
     ap.add_argument("--commit", default="")
-    ap.add_argument("--out", default="", help="default: profiles/population/rollout_time.json (rng_time.json with --rng)")
+    ap.add_argument("--out", default="", help="default: profiles/population/rollout_time.json (rng_time.json with --rng, "
+                                              "finish_time.json with --finish)")
     a = ap.parse_args()
     if a.solo_child:
         return solo_child(a.solo_child, a.envs, a.frag_len, a.repeats)
+    if a.finish or a.finish_child:
+        return main_finish(a)
     if a.rng or a.rng_child:
         return main_rng(a)
     a.out = a.out or os.path.join(HERE, "profiles", "population", "rollout_time.json")
