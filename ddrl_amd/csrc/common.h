@@ -487,8 +487,19 @@ __device__ __forceinline__ void store_act_fm(float* buf, int tile, const floatx4
 // which a single wave per SIMD cannot hide -- kept for the KSP = 1 kernels, which spill more with
 // the loads held in flight.  Either way every accumulator receives its products in the same
 // (u, v) order: the same bits (profiles/dw_streams).
-template <int NROWS, int NT_, int LD = NROWS + 8, bool AHEAD = true>
-__device__ __forceinline__ void dw_tiles_fm(const float* A, const float* B, const int* fa, int fo, floatx4* out) {
+//
+// Two streams back to back without a barrier between them (AHEAD only; the fused row split whose
+// dW1 operands have images of their own, update_dwb in ppo_ffn_impl.h): NN > 0 loads row group 0
+// of the next stream's NN tiles (images NA / NB, feature blocks nfa, the same fo) into nav / nbv,
+// dealt over the last row group's first three v sub-steps like any other group's, so they are in
+// flight under this stream's last MFMAs; PRE takes row group 0 from pav / pbv instead of loading
+// it.  Neither changes a product or the order in which an accumulator receives them.
+template <int NROWS, int NT_, int LD = NROWS + 8, bool AHEAD = true, bool PRE = false, int NN = 0>
+__device__ __forceinline__ void dw_tiles_fm(const float* A, const float* B, const int* fa, int fo, floatx4* out,
+                                            const floatx4* pav = nullptr, const floatx4* pbv = nullptr,
+                                            const float* NA = nullptr, const float* NB = nullptr,
+                                            const int* nfa = nullptr, floatx4* nav = nullptr, floatx4* nbv = nullptr) {
+  static_assert(AHEAD || (!PRE && NN == 0), "chained streams have the loads-ahead form only");
   const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
 #pragma unroll
   for (int i = 0; i < NT_; ++i) out[i] = splat4(0.f);
@@ -520,9 +531,20 @@ __device__ __forceinline__ void dw_tiles_fm(const float* A, const float* B, cons
       if (j < NT_) av[u & 1][j] = *reinterpret_cast<const floatx4*>(ap[j] + 16 * u);
       else bv[u & 1] = *reinterpret_cast<const floatx4*>(bp + 16 * u);
     };
+    auto nld = [&](int j) {   // load j of the next stream's row group 0
+      if (j < NN) nav[j] = *reinterpret_cast<const floatx4*>(NA + (16 * nfa[j] + c) * LD + 4 * q);
+      else *nbv = *reinterpret_cast<const floatx4*>(NB + (16 * fo + c) * LD + 4 * q);
+    };
     constexpr int NL = NT_ + 1, PER = (NL + 2) / 3;
+    constexpr int NNL = NN + 1, NPER = (NNL + 2) / 3;
+    if constexpr (PRE) {
 #pragma unroll
-    for (int j = 0; j < NL; ++j) ld(0, j);
+      for (int j = 0; j < NT_; ++j) av[0][j] = pav[j];
+      bv[0] = *pbv;
+    } else {
+#pragma unroll
+      for (int j = 0; j < NL; ++j) ld(0, j);
+    }
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
       __builtin_amdgcn_sched_barrier(0);
@@ -532,6 +554,13 @@ __device__ __forceinline__ void dw_tiles_fm(const float* A, const float* B, cons
 #pragma unroll
           for (int j = v * PER; j < (v + 1) * PER && j < NL; ++j) ld(u + 1, j);
           __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (NN > 0) {
+          if (u + 1 == NU && v < 3) {
+#pragma unroll
+            for (int j = v * NPER; j < (v + 1) * NPER && j < NNL; ++j) nld(j);
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
 #pragma unroll
         for (int i = 0; i < NT_; ++i) out[i] = mfma4(av[u & 1][i][v], bv[u & 1][v], out[i]);

@@ -1,6 +1,7 @@
 // Fused PPO update kernel for the fcnet model: see ppo_ffn.hip for the design notes.
 #pragma once
 #include <atomic>
+#include <type_traits>
 #include "common.h"
 #include "kernels.h"
 #include "ffn.h"
@@ -270,6 +271,20 @@ __host__ __device__ constexpr bool update_pad(int A, int ksp) { return kLdsPad &
 // update_loop): the row split on 64 rows per workgroup.  With 128 rows the images pass the
 // 160 KB of a workgroup (183 KB for A = 2), so those kernels keep the DPP reductions
 __host__ __device__ constexpr bool update_hmf(int ksp) { return ksp == 2 && DDRL_MB / ksp == 64; }
+// One barrier for the whole weight-gradient phase (DWB in update_loop): dW1's
+// operands X / dZ1 get feature-major images of their own, written before sync #1, so the dW2 and
+// dW1 tiles run as one stream with neither sync #2 nor sync #3.  The two images are 112 (ROWS + 8)
+// floats: the row split on 64 rows per workgroup up to A = DDRL_DWB_MAXA (A = 8 would need 172.9 KB).
+// The atomic-protocol and peer units (DDRL_FFN_AT) and the gradient-export launches' unit
+// (ppo_ffn_k1.hip) keep the two-barrier form: they were not timed in the new one.
+// -DDDRL_DWB_MAXA=0 builds the old form everywhere for A/B timing.
+#ifndef DDRL_DWB_MAXA
+#define DDRL_DWB_MAXA 4
+#endif
+static_assert(DDRL_DWB_MAXA <= 4, "the A = 8 kernels have no LDS for the X / dZ1 images");
+__host__ __device__ constexpr bool update_dwb(int A, int ksp) {
+  return !DDRL_FFN_AT && DDRL_FFN_KSP != 1 && ksp == 2 && DDRL_MB / ksp == 64 && A <= DDRL_DWB_MAXA;
+}
 
 // "Small" parameters owned one per thread: [dWo 64*OB][dbo OB][db1 64][db2 64], then the
 // policy branch's leg-coupling table [4][A] of the "cup" model
@@ -800,10 +815,14 @@ __device__ __forceinline__ void head_bwd_mfma(const NetLds& W, const float* dout
 // MFMA stream (the policy head's dWo = H2^T dout tile of feature block fah, dout image
 // rows >= 2A zero): out[i] as dw_tiles_fm, outh[r] = dWo[16 fah + 4q + r][o = c].
 // Only the row split (KSP = 2) runs the head on MFMA, so this helper has the loads-ahead form of
-// dw_tiles_fm (common.h) alone.
-template <int NROWS, int NT_, int LD = NROWS + 8>
+// dw_tiles_fm (common.h) alone.  NN > 0: row group 0 of the next stream's operands is loaded
+// under the last row group's MFMAs, as in dw_tiles_fm.
+template <int NROWS, int NT_, int LD = NROWS + 8, int NN = 0>
 __device__ __forceinline__ void dw_tiles_fm_head(const float* A, const float* B, const int* fa, int fo, floatx4* out,
-                                                 const float* AH, const float* BH, int fah, floatx4& outh) {
+                                                 const float* AH, const float* BH, int fah, floatx4& outh,
+                                                 const float* NA = nullptr, const float* NB = nullptr,
+                                                 const int* nfa = nullptr, floatx4* nav = nullptr,
+                                                 floatx4* nbv = nullptr) {
   const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
 #pragma unroll
   for (int i = 0; i < NT_; ++i) out[i] = splat4(0.f);
@@ -822,7 +841,12 @@ __device__ __forceinline__ void dw_tiles_fm_head(const float* A, const float* B,
     else if (j == NT_ + 1) ahv[u & 1] = *reinterpret_cast<const floatx4*>(aph + 16 * u);
     else bhv[u & 1] = *reinterpret_cast<const floatx4*>(bph + 16 * u);
   };
+  auto nld = [&](int j) {   // load j of the next stream's row group 0
+    if (j < NN) nav[j] = *reinterpret_cast<const floatx4*>(NA + (16 * nfa[j] + c) * LD + 4 * q);
+    else *nbv = *reinterpret_cast<const floatx4*>(NB + (16 * fo + c) * LD + 4 * q);
+  };
   constexpr int NL = NT_ + 3, PER = (NL + 2) / 3;
+  constexpr int NNL = NN + 1, NPER = (NNL + 2) / 3;
 #pragma unroll
   for (int j = 0; j < NL; ++j) ld(0, j);
 #pragma unroll
@@ -834,6 +858,13 @@ __device__ __forceinline__ void dw_tiles_fm_head(const float* A, const float* B,
 #pragma unroll
         for (int j = v * PER; j < (v + 1) * PER && j < NL; ++j) ld(u + 1, j);
         __builtin_amdgcn_sched_barrier(0);
+      }
+      if constexpr (NN > 0) {
+        if (u + 1 == NU && v < 3) {
+#pragma unroll
+          for (int j = v * NPER; j < (v + 1) * NPER && j < NNL; ++j) nld(j);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
 #pragma unroll
       for (int i = 0; i < NT_; ++i) out[i] = mfma4(av[u & 1][i][v], bv[u & 1][v], out[i]);
@@ -890,7 +921,26 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
   constexpr bool HMF = POL && update_hmf(KSP);
   float* bufH = red + 256;                  // HMF: feature-major [64][LD] H2
   float* bufD = bufH + 64 * LD;             // HMF: feature-major [16][LD] dout
-  float* stg = red + 256 + (HMF ? 80 * LD : 0);   // [ROWS][stride] records of the next step (16 B aligned)
+  // DWB: dW1's operands in images of their own, so nothing is rewritten between the dW2 and the
+  // dW1 tiles and a wave runs them as one stream behind sync #1.  Lifetimes (barriers of a step:
+  // #1, #4, #5, #6; wider heads keep #2 for their small parameters):
+  //   bufX / bufZ1: written before sync #1, read by every wave until its dW1 tiles end (before it
+  //     arrives at sync #4), next written after sync #6 of the same step;
+  //   bufA / bufB / bufH / bufD: written before sync #1, read until a wave's dW2 tiles end, next
+  //     written after syncs #4 - #6;
+  //   stg as before: read at the step head, gathers fired after sync #4.
+  constexpr bool DWB = update_dwb(A, KSP);
+  // DWB, A = 2 policy branch: slot 0 of the small parameters is exactly the 256 head weights, and
+  // element e = 64 w + 16 q + 4 r + c of it comes out of wave w's own head tile for lane tid = e of
+  // the same wave (the other waves' rows of that slot are zero): no barrier between the head tile
+  // and the puts.  Wider heads own head elements across waves and keep sync #2 for put_small().
+  constexpr bool SMB = DWB && HMF && 64 * OB == NT;
+  constexpr bool KEEP2 = DWB && HMF && !SMB;
+  // row group 0 of the dW1 operands loaded under the last dW2 MFMAs (no barrier in between)
+  constexpr bool DWPRE = DWB && !KEEP2 && DWF;
+  float* bufX = red + 256 + (HMF ? 80 * LD : 0);   // DWB: feature-major [48][LD] X
+  float* bufZ1 = bufX + 48 * LD;                   // DWB: feature-major [64][LD] dZ1
+  float* stg = red + 256 + (HMF ? 80 * LD : 0) + (DWB ? 112 * LD : 0);   // [ROWS][stride] records of the next step (16 B aligned)
   const int stride = U.lay.stride, cpr = stride >> 2, cpr_l = stg_chunks(stride, A);
   const float inv_cpr_l = 1.f / (float)cpr_l;
 
@@ -1002,6 +1052,14 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     // division) early: its latency hides under the forward's MFMAs
     const float alpha = H.lr * sqrtf(1.f - b2p) / (1.f - b1p);
     load_row<A, KS1, POL, RT>(stg, 4 * cpr_l, U.lay, row_l, d, cur, xlast_bits);
+    // DWB: X, dW1's first operand, into its image at once -- cur.x is then dead behind layer 1
+    // (stored beside the H1 / dZ2 stores instead: the same time, 9 more AGPRs in <2,9>)
+    if constexpr (DWB) {
+#pragma unroll
+      for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int s = 0; s < 12; ++s) bufX[(4 * s + q) * LD + row_l[t]] = cur.x[t][s];
+    }
     // ---- forward + loss + output gradient (two row tiles) ----
     floatx4 h1[RT][4], h2[RT][4], dz[RT][4];
     float out[RT][OB], dout[RT][OB];
@@ -1144,8 +1202,11 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
         }
       Pw[64 * OB + OB + h_own] = row16_transpose_sum(v);          // db1
     }
+    if constexpr (DWB)
+#pragma unroll
+      for (int t = 0; t < RT; ++t) store_act_fm<LD>(bufZ1, RT * w + t, h2[t]);
     STAMP(4);
-    __syncthreads();                                     // #1: H1, dZ2, partials visible
+    __syncthreads();                                     // #1: H1, dZ2, partials (DWB: X, dZ1) visible
     STAMP(5);
     const unsigned gtag = xchg_tag(ub.epoch, step);
     const int gstep = step + (int)ub.lx_base;            // outbox parity and quad tag bit
@@ -1158,12 +1219,23 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
     // small-parameter partials and this half's loss statistics into the exchange (KSP = 2):
     // first thing after sync #1, or -- policy branch, whose head tile lands in the partials
     // with the dW2 tiles -- after sync #2 (all pairs are polled together, after the dW1 tiles)
-    auto put_small = [&] {
+    // (SMB: the sums of slots 1 .. and the statistics first thing after sync #1, slot 0 from the
+    // wave's own head tile, the puts right behind it)
+    // phase 0: the sums, then the puts (the two-barrier form, and every value branch).  SMB: phase 1,
+    // the sums of slots 1 .. and the statistics, then phase 2, the puts with slot 0 in gs[0]
+    auto put_small_ph = [&](auto phase) {
+      constexpr int PH = decltype(phase)::value;
       float v0[2 * NP0];
 #pragma unroll
       for (int k = 0; k < 2 * NP0; ++k) v0[k] = 0.f;
 #pragma unroll
       for (int k = 0; k < NSLOT; ++k) {
+        if constexpr (PH != 0) {
+          if (PH == 2 || k == 0) {
+            v0[k] = gs[k];
+            continue;
+          }
+        }
         const int e = tid + NT * k;
         float sm = 0.f;
         if (e < nsb)
@@ -1171,8 +1243,11 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
         gs[k] = sm;
         v0[k] = sm;
       }
-      if (tid < NSTAT)
-        for (int i = 0; i < NW; ++i) st_own += red[i * 8 + tid];
+      if constexpr (PH != 2) {
+        if (tid < NSTAT)
+          for (int i = 0; i < NW; ++i) st_own += red[i * 8 + tid];
+      }
+      if constexpr (PH == 1) return;
       v0[NSLOT] = st_own;
 #if DDRL_LX_ON
       if constexpr (LX) {
@@ -1188,24 +1263,42 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
 #pragma unroll
       for (int j = 0; j < NP0; ++j) gx_put(gx_mine, j, v0[2 * j], v0[2 * j + 1], gtag, coh);
     };
+    auto put_small = [&] { put_small_ph(std::integral_constant<int, 0>()); };
     if constexpr (KSP == 2 && !HMF) put_small();
+    if constexpr (SMB) put_small_ph(std::integral_constant<int, 1>());
     floatx4 gt[NTS];
     RowGather<NW, ROWS> G;   // row split: the next step's gathers, prepared under the partner poll
     (void)G;
+    // DWPRE: row group 0 of the dW1 stream's operands (all NS2 tile slots: a slot past the valid
+    // prefix reads feature rows < 48 of bufX and is not used), loaded under the last dW2 MFMAs
+    floatx4 pav[NS2], pbv;
+    (void)pav; (void)pbv;
 #ifndef DDRL_ABL_NO_DW2   // ablation builds (timing only): skip a phase
     if constexpr (HMF) {
       static_assert(NW == 4, "one head tile (16 features) per wave");
       static_assert(DWF, "the head tile's helper has the loads-ahead form only");
       floatx4 gh;
-      dw_tiles_fm_head<ROWS, NS1, ROWS + 8>(bufA, bufB, tfa, w & 3, gt, bufH, bufD, w, gh);   // dW2 tiles + dWo
+      if constexpr (DWPRE)
+        dw_tiles_fm_head<ROWS, NS1, ROWS + 8, NS2>(bufA, bufB, tfa, w & 3, gt, bufH, bufD, w, gh, bufX, bufZ1, tfa + NS1,
+                                                   pav, &pbv);   // dW2 tiles + dWo
+      else
+        dw_tiles_fm_head<ROWS, NS1, ROWS + 8>(bufA, bufB, tfa, w & 3, gt, bufH, bufD, w, gh);   // dW2 tiles + dWo
       if (c < OB)
 #pragma unroll
         for (int r = 0; r < 4; ++r) Pb[(16 * w + 4 * q + r) * OB + c] = gh[r];
     } else {
-      dw_tiles_fm<ROWS, NS1, ROWS + 8, DWF>(bufA, bufB, tfa, w & 3, gt);   // dW2 tiles of this wave
+      if constexpr (DWPRE)
+        dw_tiles_fm<ROWS, NS1, ROWS + 8, DWF, false, NS2>(bufA, bufB, tfa, w & 3, gt, nullptr, nullptr, bufX, bufZ1,
+                                                          tfa + NS1, pav, &pbv);   // dW2 tiles of this wave
+      else
+        dw_tiles_fm<ROWS, NS1, ROWS + 8, DWF>(bufA, bufB, tfa, w & 3, gt);   // dW2 tiles of this wave
     }
 #else
     for (int i = 0; i < NS1; ++i) gt[i] = splat4(0.f);
+    if constexpr (DWPRE) {   // (the dW1 stream still gets its first operands)
+      for (int i = 0; i < NS2; ++i) pav[i] = *reinterpret_cast<const floatx4*>(bufX + (16 * tfa[NS1 + i] + c) * LD + 4 * q);
+      pbv = *reinterpret_cast<const floatx4*>(bufZ1 + (16 * (w & 3) + c) * LD + 4 * q);
+    }
 #endif
     if constexpr (KSP == 2) {
 #pragma unroll
@@ -1221,17 +1314,29 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
         gx_put(gx_mine, NP0 + 2 * i + 1, gt[i][2], gt[i][3], gtag, coh);
       }
     }
-    STAMP(6);
-    __syncthreads();                                     // #2: dW2 operands consumed
-    if constexpr (HMF) put_small();
-    STAMP(7);
-#pragma unroll
-    for (int t = 0; t < RT; ++t) {
-      store_act_fm<LD>(bufB, RT * w + t, h2[t]);
-#pragma unroll
-      for (int s = 0; s < 12; ++s) bufA[(4 * s + q) * LD + row_l[t]] = cur.x[t][s];
+    if constexpr (SMB) {
+      // this lane's head weight from its own wave's tile, behind the dW2 puts (which hide the round
+      // trip): a wave's LDS operations are ordered, so the read-back needs no barrier.  0 + x: a -0
+      // becomes +0, as the sum over the NW partial rows (x and NW - 1 zeros) made it
+      __builtin_amdgcn_wave_barrier();
+      gs[0] = 0.f + Pb[tid];
+      put_small_ph(std::integral_constant<int, 2>());
     }
-    __syncthreads();                                     // #3: X, dZ1 visible
+    STAMP(6);
+    // (DWB: the images of dW1's operands were written before sync #1; only the wider heads' small
+    // parameters still wait for every wave's head tile)
+    if constexpr (!DWB || KEEP2) __syncthreads();        // #2: dW2 operands consumed
+    if constexpr (HMF && !SMB) put_small();
+    STAMP(7);
+    if constexpr (!DWB) {
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        store_act_fm<LD>(bufB, RT * w + t, h2[t]);
+#pragma unroll
+        for (int s = 0; s < 12; ++s) bufA[(4 * s + q) * LD + row_l[t]] = cur.x[t][s];
+      }
+      __syncthreads();                                   // #3: X, dZ1 visible
+    }
     STAMP(8);
     // ---- prefetch: the records of step + 1 land in stg (LDS-DMA) while the dW1 tiles, the
     //      norm exchange and Adam run; every lane has read its rows of this step (sync #1).
@@ -1260,11 +1365,24 @@ __device__ __forceinline__ void update_loop(const UpdateArgs& U, const UpdateBat
 #ifdef DDRL_ABL_NO_DW1
       n1 = -1;
 #endif
-      if (n1 == NS2) dw_tiles_fm<ROWS, NS2, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
-      else if constexpr (NS2 >= 3) {
-        if (n1 == 2) dw_tiles_fm<ROWS, 2, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
-        else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
-      } else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+      if constexpr (!DWB) {
+        if (n1 == NS2) dw_tiles_fm<ROWS, NS2, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+        else if constexpr (NS2 >= 3) {
+          if (n1 == 2) dw_tiles_fm<ROWS, 2, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+          else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+        } else if (n1 == 1) dw_tiles_fm<ROWS, 1, ROWS + 8, DWF>(bufA, bufB, tfa + NS1, w & 3, gt + NS1);
+      } else {
+        // from the images of their own; DWPRE: row group 0 is already in registers
+        auto dw1 = [&](auto nt) {
+          constexpr int N1 = decltype(nt)::value;
+          dw_tiles_fm<ROWS, N1, ROWS + 8, DWF, DWPRE>(bufX, bufZ1, tfa + NS1, w & 3, gt + NS1, pav, &pbv);
+        };
+        if (n1 == NS2) dw1(std::integral_constant<int, NS2>());
+        else if constexpr (NS2 >= 3) {
+          if (n1 == 2) dw1(std::integral_constant<int, 2>());
+          else if (n1 == 1) dw1(std::integral_constant<int, 1>());
+        } else if (n1 == 1) dw1(std::integral_constant<int, 1>());
+      }
     }
     STAMP(10);
     if constexpr (KSP == 2) {
@@ -1605,18 +1723,28 @@ __global__ void __launch_bounds__(64 * waves_for(A, KSP)) k_update_ffn(UpdateBat
 #endif   // !DDRL_FFN_GROUP
 
 // stride: the widest record stride of the launched policies (staging buffer rows)
-static size_t update_lds_bytes(int O, int stride, int ksp) {
+static constexpr size_t update_lds_bytes(int O, int stride, int ksp) {
   const int nsb = 64 * O + O + 128 + ncup_slots(O, true);
   const int nw = waves_for(O / 2, ksp);
   // + the policy head's H2 / dout images of the row split (HMF in update_loop)
+  // + the X / dZ1 images of the one-barrier weight-gradient phase (DWB in update_loop)
   return (size_t)(branch_lds_floats(update_pad(O / 2, ksp)) + 2 * 64 * (DDRL_MB / ksp + 8) + nw * nsb + 256 +
                   (update_hmf(ksp) ? 80 * (DDRL_MB / ksp + 8) : 0) +
+                  (update_dwb(O / 2, ksp) ? (48 + 64) * (DDRL_MB / ksp + 8) : 0) +
                   (DDRL_MB / ksp) * 4 * stg_chunks(stride, O / 2)) * 4;
+}
+// A launch over the 160 KB of a workgroup is refused at run time (invalid argument), so every
+// dispatched <A, KS1> instance that takes the X / dZ1 images is checked here at its widest record:
+// d = 4 KS1 observation columns, then actions, logits, logp, vf, adv, vt, reward (+ the leg row)
+template <int A, int KS1, bool CUP>
+constexpr bool update_lds_fits() {
+  return !update_dwb(A, 2) || update_lds_bytes(2 * A, (4 * KS1 + 3 * A + 5 + (CUP ? 1 : 0) + 3) & ~3, 2) <= 160 * 1024;
 }
 
 #if DDRL_FFN_GROUP
 template <int A, int KS1, bool CUP = false>
 static void launch_group_t(hipStream_t s, GroupBatch& gb, int stride, int grid) {
+  static_assert(update_lds_fits<A, KS1, CUP>(), "X / dZ1 images: past the 160 KB of LDS at the widest record");
   gb.b.lds_bytes = (unsigned)update_lds_bytes(2 * A, stride, 2);
   hipLaunchKernelGGL((k_update_ffn_group<A, KS1, CUP>), dim3(grid), dim3(64 * waves_for(A, 2)), gb.b.lds_bytes, s, gb);
 }
@@ -1658,6 +1786,7 @@ int launch_update_ffn_group(hipStream_t s, const UpdateArgs* table_dev, int n_ch
 #else
 template <int A, int KS1, bool CUP = false>
 static void launch_update_t(hipStream_t s, UpdateBatch& ub, int P, int stride, int ksp, bool lx) {
+  static_assert(update_lds_fits<A, KS1, CUP>(), "X / dZ1 images: past the 160 KB of LDS at the widest record");
   ub.lds_bytes = (unsigned)update_lds_bytes(2 * A, stride, ksp);
 #if DDRL_FFN_KSP != 1
   if (ksp == 2 && lx)

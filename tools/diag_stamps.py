@@ -50,8 +50,11 @@ split = os.environ.get("DDRL_UPDATE_SPLIT", "2") != "1"
 blocks = [0, 8, 16] if split else [0, 8]
 labels = ["policy rows 0-63", "policy rows 64-127", "value rows 0-63"] if split else ["policy", "value"]
 a = np.array(st, dtype=np.float64).reshape(32, 16)[blocks, :15] / steps
-names = ["fwd", "loss", "dpp head/bias", "head bwd+db2+stores", "layer2 bwd+db1", "sync#1 (+gs/stats out)",
-         "dW2 tiles (+out)", "sync#2", "X/dZ1 stores + sync#3", "prefetch issue", "dW1 tiles",
+# The one-barrier weight-gradient phase (update_dwb, ppo_ffn_impl.h) has neither sync #2 nor the
+# store block and sync #3: its X store sits in "fwd" (step head), its dZ1 stores in "layer2 bwd+db1",
+# the policy's small-parameter puts in "dW2 tiles (+out)", and the two stamps between are empty.
+names = ["fwd", "loss", "dpp head/bias", "head bwd+db2+stores", "layer2 bwd+db1 (+dZ1 stores)", "sync#1 (+gs/stats out)",
+         "dW2 tiles (+out)", "sync#2 (two-barrier form)", "X/dZ1 stores + sync#3 (two-barrier form)", "prefetch issue", "dW1 tiles",
          "norm exchange", "adam", "sync#6", "partner exchange (split)"]
 print(f"steps {steps}, {dt / steps * 1e6:.2f} us/step wall")
 if hasattr(N.load(), "ddrl_diag_poll_stale"):
